@@ -2,16 +2,20 @@
 """Headline benchmark: FastVim-T 224x224 bs=128/GPU bf16 training step (fwd + loss + bwd
 [+ gradient all-reduce] + AdamW) on MI355X, images/sec whole-job.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement) that also carries
-  "roofline":     the dominant hand-written kernel, timed live with HIP events on the launch stream,
+Rank 0 prints ONE JSON line: images/s and ms_per_step of exactly --steps timed steps after --warmup untimed ones.
+A plain run does nothing else.  ``--dump-outputs DIR`` writes what the last timed step computed (loss, parameters,
+gradients, EMA weights) as DIR/<name>.npy.  ``--full`` adds to the line
+  "kernels", "roofline": every hand-written kernel of a block, timed live with HIP events on the launch stream,
                   against its algorithmic HBM bytes (DESIGN.md section "Kernels and rooflines");
   "cpu_baseline": the CPU oracle (a port of the reference's pure-PyTorch path, selective_scan_ref
-                  included) timed on this host on a bounded sample of the same workload.
-Synthetic data: ImageNet-shaped N(0,1) pixels, Mixup-like soft targets; random-init weights.
+                  included) timed on this host on a bounded sample of the same workload;
+  "scan_op", "other_configs": the scan op at every configuration's shape, the other configurations and baselines.
+Synthetic data: ImageNet-shaped N(0,1) pixels, Mixup-like soft targets; random-init weights, all seeded: the same
+arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -665,10 +669,12 @@ def scan_op_table(cpu=True):
 
 
 def run_training_steps(model_name, img, batch, channels, dtype, steps, warmup, rank, world, dev, use_graph=True,
-                       trace=False, buckets=3, comm_dtype=None, force_segmented=False):
+                       trace=False, buckets=3, comm_dtype=None, force_segmented=False, keep_outputs=False):
     """Build the model + flat training state + fused optimizer, capture the whole step (fwd + loss + bwd + AdamW + EMA;
     the gradient exchange sits between graph replay and optimizer when world > 1) and time exactly ``steps`` steps
-    after ``warmup`` untimed ones, bracketed by barrier + synchronize.  Returns (seconds, final loss, extras)."""
+    after ``warmup`` untimed ones, bracketed by barrier + synchronize.  Returns (seconds, final loss, extras).
+    ``keep_outputs``: extras["outputs"] holds what the last timed step left its caller (CPU copies, taken after the
+    timed region): the loss, the flat fp32 parameters, their gradient and the EMA weights."""
     from fastvim_amd.flat import FlatAdamW, FlatTrainingState
     from fastvim_amd.losses import SoftTargetCrossEntropy
 
@@ -772,6 +778,9 @@ def run_training_steps(model_name, img, batch, channels, dtype, steps, warmup, r
     loss_val = float(loss)
     n_params = sum(p.numel() for p in model.parameters())
     extras = {"params": n_params}
+    if keep_outputs:
+        extras["outputs"] = {"loss": loss.detach().float().reshape(1).cpu(), "params": flat.param_flat.cpu(),
+                             "grads": flat.grad_flat.cpu(), "ema": opt.ema.cpu()}
     if world > 1:
         ex = getattr(flat, "exchange", None)
         # what every rank ran on, gathered so that the first SCALE record is self-describing: device index, device name,
@@ -944,6 +953,22 @@ def vim_vs_fastvim_block(dev, img=2048, batch=8):
 
 
 # --------------------------------------------------------------------------- main
+DUMP_MAX_ELEMS = 1 << 22      # per array (16 MiB of float32): the four arrays of a dump stay under 64 MB
+
+
+def dump_outputs(out_dir, outputs):
+    """Write each array of ``outputs`` as ``out_dir/<name>.npy``, flattened, in float32.  An array longer than
+    DUMP_MAX_ELEMS is replaced by a fixed sample: its elements at DUMP_MAX_ELEMS ascending indices drawn with seed 0
+    from its length, so two runs of the same configuration write the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        a = t.float().reshape(-1).numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(n):
     """``python bench.py --gpus N`` without a launcher: run ``python -m torch.distributed.run --nnodes=1
     --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>`` as a CHILD process
@@ -981,7 +1006,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--kernels", action="store_true",
-                    help="N > 1: time the kernel table as well (rank 0, after the timed region, the other ranks parked in a "
+                    help="N > 1 with --full: time the kernel table as well (rank 0, after the timed region, the other ranks parked in a "
                          "barrier -- off by default there: the scaling run stays short and no rank idles next to a busy one)")
     ap.add_argument("--buckets", type=int, default=3,
                     help="N > 1: gradient buckets = backward graph segments the all-reduce overlaps with (0: one all-reduce after backward)")
@@ -1003,7 +1028,14 @@ def main():
     ap.add_argument("--vim-2048", action="store_true", help="only the Vim-vs-FastVim block at 2048 px (SURVEY row f2), as JSON")
     ap.add_argument("--no-scan-op", action="store_true",
                     help="skip timing the reference-layout op selective_scan_fn at every config's (B, d_in, Lc, N)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: kernel table and rooflines, CPU baseline, scan op, "
+                         "other configurations (the --no-* switches above then leave parts out); a plain run times the step only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (loss, parameters, gradients, EMA) as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        args.no_kernels = args.no_cpu_baseline = args.no_scan_op = args.no_other_configs = True
     if args.gpus > 1 and not args.kernels:
         args.no_kernels = True
         args.no_other_configs = True
@@ -1061,9 +1093,12 @@ def main():
     elapsed, loss_val, extras = run_training_steps(args.model, args.img, args.batch, args.channels, args.dtype, args.steps,
                                                    args.warmup, rank, world, dev, use_graph=use_graph, trace=trace,
                                                    buckets=args.buckets, comm_dtype=comm_dtype,
-                                                   force_segmented=args.segmented)
+                                                   force_segmented=args.segmented,
+                                                   keep_outputs=bool(args.dump_outputs) and rank == 0)
     if not (loss_val == loss_val):
         raise SystemExit("non-finite loss in the timed region")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, extras.pop("outputs"))
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3

@@ -15,15 +15,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.parametrize("kernel_rows", [False, True])
 def test_two_rank_bench_line(kernel_rows):
-    """kernel_rows: ``--kernels`` -- rank 0 times its kernel table (graph captures of its own) while the process group is
-    alive and the other rank waits in the closing barrier.  Without the flag an N > 1 line carries no kernel table (round
-    5: the scaling run stays short and no rank idles beside a busy one)."""
+    """kernel_rows: ``--full --kernels`` -- rank 0 times its kernel table (graph captures of its own) while the process
+    group is alive and the other rank waits in the closing barrier.  Without the flags an N > 1 line carries no kernel
+    table (round 5: the scaling run stays short and no rank idles beside a busy one)."""
     env = dict(os.environ, FASTVIM_BENCH_ONE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29538" if kernel_rows else "29537", os.path.join(ROOT, "bench.py"), "--gpus", "2",
            "--steps", "3", "--warmup", "1", "--batch", "16", "--no-cpu-baseline", "--no-scan-op"]
     if kernel_rows:
-        cmd.append("--kernels")
+        cmd += ["--full", "--kernels"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
