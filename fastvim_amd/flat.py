@@ -317,15 +317,81 @@ class FlatTrainingState:
         self.exchange.allreduce_(mean=mean)
 
 
+MAX_PARAM_GROUPS = 256          # one group byte per element (csrc/optim.hip: adamw_flat_groups_kernel)
+
+
+def build_group_map(names, offsets, sizes, total, groups, default_weight_decay=0.0):
+    """The group byte of every element of the flat layout and the table the bytes index -- a pure function (no device,
+    no model): ``names`` are the flat state's parameter names, ``offsets`` / ``sizes`` their first element and element
+    count (dicts by name), ``total`` the padded length, ``groups`` a list of dicts with ``"params"`` (names), optional
+    ``"lr_scale"`` (default 1) and ``"weight_decay"`` (default ``default_weight_decay``).
+
+    Returns ``(ids, table, per_name)``: a CPU uint8 tensor of ``total`` bytes (padding between parameters = row 0), the
+    list of distinct ``(lr_scale, weight_decay)`` rows in first-seen order (groups with equal values share a row) and the
+    row values by parameter name.  ``ValueError`` for a parameter in two groups, a name the flat state does not hold, a
+    parameter of the flat state in no group, or more than 256 distinct rows."""
+    known = set(names)
+    rows, table, per_name = {}, [], {}
+    ids = torch.zeros(total, dtype=torch.uint8)
+    for g in groups:
+        key = (float(g.get("lr_scale", 1.0)), float(g.get("weight_decay", default_weight_decay)))
+        for n in g["params"]:
+            if n not in known:
+                raise ValueError(f"param_groups: {n!r} is not a trainable parameter of the flat training state")
+            if n in per_name:
+                raise ValueError(f"param_groups: parameter {n!r} appears in more than one group")
+            if key not in rows:
+                if len(table) == MAX_PARAM_GROUPS:
+                    raise ValueError(f"param_groups: more than {MAX_PARAM_GROUPS} distinct (lr_scale, weight_decay) pairs "
+                                     "(the fused optimizer keeps one group byte per element)")
+                rows[key] = len(table)
+                table.append(key)
+            per_name[n] = key
+            ids[offsets[n]:offsets[n] + sizes[n]] = rows[key]
+    missing = [n for n in names if n not in per_name]
+    if missing:
+        raise ValueError(f"param_groups: {len(missing)} trainable parameters of the flat training state are in no group: "
+                         f"{missing[:4]} ...")
+    return ids, table, per_name
+
+
+def groups_from_named(per_name):
+    """Inverse of ``build_group_map``'s ``per_name`` (what ``FlatAdamW.state_dict()["param_groups"]`` stores): groups of
+    parameter NAMES, one per distinct ``(lr_scale, weight_decay)``, in first-seen order."""
+    out = {}
+    for n, (scale, wd) in per_name.items():
+        key = (float(scale), float(wd))
+        out.setdefault(key, {"lr_scale": key[0], "weight_decay": key[1], "params": []})["params"].append(n)
+    return list(out.values())
+
+
 class FlatAdamW:
     """torch.optim.AdamW semantics as ONE HIP kernel over a FlatTrainingState (csrc/optim.hip): AdamW
     update, optional EMA of the weights (timm ModelEmaV2) and the bf16 shadow refresh in a single pass.
     ``no_decay`` is a set of parameter names excluded from weight decay (reference recipe:
     imagenet_classification/utils.py:52-69).  ``lr`` may be changed between steps with ``set_lr`` --
-    it lives in device memory, so a captured HIP graph replays with the new value."""
+    it lives in device memory, so a captured HIP graph replays with the new value.
+
+    The fine-tune recipe (mae/finetune_imagenet.py:238-262, mae/config/finetune_FastVimH_448.yaml) -- any of the three
+    arguments below switches ``step()`` from ``fv_adamw_flat`` to ``fv_adamw_flat_groups``; with none of them the object
+    is exactly what it was:
+
+    * ``param_groups``: torch-style groups, ``"params"`` (parameters or names) with optional ``"lr_scale"`` (default 1)
+      and ``"weight_decay"`` (default: the constructor's) -- what ``fastvim_amd.lr_decay.param_groups_lrd`` returns goes
+      in unchanged (``no_decay`` is then unused: the groups say it).  ``set_lr`` keeps setting the BASE lr; a group
+      trains at ``lr * lr_scale``.  The ``(lr_scale, weight_decay)`` rows live on the device as ``group_table`` and may be
+      written between steps.  Without it: two groups, from ``weight_decay`` and ``no_decay``.
+    * ``max_grad_norm``: clip the global L2 norm of the gradient, ``torch.nn.utils.clip_grad_norm_`` semantics
+      (``clip_coef = min(1, max_norm / (norm + 1e-6))``), computed on the device in one extra launch
+      (``set_max_grad_norm`` changes it; a captured graph replays with the new value).  The norm is that of the gradient
+      AS THE STEP READS IT: with ``step(grad_scale=1 / world)`` after a sum all-reduce it is the norm of the MEAN
+      gradient -- what Lightning clips under DDP -- and every rank computes it from the same all-reduced buffer, so no
+      collective is added.
+    * ``skip_nonfinite``: a step whose gradient norm is not finite changes nothing (parameters, moments, EMA, shadow,
+      step count) and is counted in ``last_stats()["skipped_steps"]``."""
 
     def __init__(self, flat, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, no_decay=(),
-                 ema_decay=None):
+                 ema_decay=None, param_groups=None, max_grad_norm=None, skip_nonfinite=False):
         self.flat = flat
         dev = flat.param_flat.device
         n = flat.param_flat.numel()
@@ -333,20 +399,78 @@ class FlatAdamW:
         self.exp_avg_sq = torch.zeros(n, device=dev, dtype=torch.float32)
         self.ema = flat.param_flat.clone() if ema_decay is not None else None
         self.ema_decay = float(ema_decay or 0.0)
-        mask = torch.zeros(n, dtype=torch.uint8)
-        named = dict(model.named_parameters())
         no_decay = set(no_decay)
-        for name, off in flat.offsets.items():
-            p = named[name]
-            if name not in no_decay:
-                mask[off:off + p.numel()] = 1
-        self.decay_mask = mask.to(dev)
         self.lr = torch.full((1,), float(lr), device=dev, dtype=torch.float32)
         self.step_t = torch.zeros(1, device=dev, dtype=torch.float32)
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._grouped = param_groups is not None or max_grad_norm is not None or self.skip_nonfinite
+        self.group_ids = self.group_table = self.max_norm = self.partials = self.stats = None
+        self._group_row_of = None
+        self.decay_mask = None
+        if not self._grouped:
+            mask = torch.zeros(n, dtype=torch.uint8)
+            named = dict(model.named_parameters())
+            for name, off in flat.offsets.items():
+                if name not in no_decay:
+                    mask[off:off + named[name].numel()] = 1
+            self.decay_mask = mask.to(dev)
+        else:
+            if param_groups is None:
+                groups = [{"params": [nm for nm in flat.names if nm not in no_decay], "weight_decay": weight_decay},
+                          {"params": [nm for nm in flat.names if nm in no_decay], "weight_decay": 0.0}]
+                groups = [g for g in groups if g["params"]]
+            else:
+                name_of = {id(p): nm for nm, p in zip(flat.names, flat._params)}
+                groups = []
+                for g in param_groups:
+                    names = []
+                    for q in g["params"]:
+                        nm = q if isinstance(q, str) else name_of.get(id(q))
+                        if nm is None:
+                            raise ValueError("param_groups: a parameter of a group is not a trainable parameter of the "
+                                             "flat training state")
+                        names.append(nm)
+                    groups.append({**g, "params": names})
+            # all 256 rows are allocated (rows past the used ones: lr_scale 0), so that loading a checkpoint with other
+            # groups rewrites the table and the bytes IN PLACE and a captured graph stays valid
+            self._group_table_full = torch.zeros(MAX_PARAM_GROUPS, 2, device=dev, dtype=torch.float32)
+            self.group_ids = torch.zeros(n, device=dev, dtype=torch.uint8)
+            self._set_groups(groups)
+            if max_grad_norm is not None or self.skip_nonfinite:
+                G = int(L.lib().fv_grad_sumsq_blocks(ctypes.c_size_t(n)))
+                self.partials = torch.zeros(G, device=dev, dtype=torch.float32)
+                self.stats = torch.zeros(4, device=dev, dtype=torch.float32)      # [total_norm, clip_coef, finite, skipped_steps]
+            if max_grad_norm is not None:
+                self.max_norm = torch.full((1,), float(max_grad_norm), device=dev, dtype=torch.float32)
+
+    def _set_groups(self, groups):
+        f = self.flat
+        sizes = {nm: p.numel() for nm, p in zip(f.names, f._params)}
+        ids, table, per_name = build_group_map(f.names, f.offsets, sizes, f.param_flat.numel(), groups, self.weight_decay)
+        rows = {key: i for i, key in enumerate(table)}
+        with torch.no_grad():
+            self.group_ids.copy_(ids)
+            self._group_table_full.zero_()
+            self._group_table_full[:len(table)].copy_(torch.tensor(table, dtype=torch.float32).view(-1, 2))
+        self._group_row_of = {nm: rows[key] for nm, key in per_name.items()}
+        self.group_table = self._group_table_full[:len(table)]     # (rows, 2) view: (lr_scale, weight_decay), writable
 
     def set_lr(self, lr):
         self.lr.fill_(float(lr))
+
+    def set_max_grad_norm(self, v):
+        if self.max_norm is None:
+            raise RuntimeError("FlatAdamW was built without max_grad_norm")
+        self.max_norm.fill_(float(v))
+
+    def last_stats(self):
+        """``{"total_norm", "clip_coef", "finite", "skipped_steps"}`` of the last step: one device-to-host read (it
+        synchronises; ``step`` never calls it)."""
+        if self.stats is None:
+            raise RuntimeError("FlatAdamW was built without max_grad_norm / skip_nonfinite: no gradient norm is computed")
+        t, c, fin, sk = self.stats.tolist()
+        return {"total_norm": t, "clip_coef": c, "finite": bool(fin), "skipped_steps": int(sk)}
 
     # ------------------------------------------------------------------ checkpoint I/O
     def _named_slices(self, buf):
@@ -361,7 +485,36 @@ class FlatAdamW:
         return {"state": {n: {"exp_avg": ea[n].detach().clone(), "exp_avg_sq": es[n].detach().clone()} for n in ea},
                 "step": float(self.step_t.item()), "lr": float(self.lr.item()), "betas": tuple(self.betas),
                 "eps": self.eps, "weight_decay": self.weight_decay, "ema_decay": self.ema_decay,
-                "ema": None if self.ema is None else {n: v.detach().clone() for n, v in self._named_slices(self.ema).items()}}
+                "ema": None if self.ema is None else {n: v.detach().clone() for n, v in self._named_slices(self.ema).items()},
+                **self._group_state()}
+
+    def _group_state(self):
+        """The new keys of ``state_dict``: ``param_groups`` (``(lr_scale, weight_decay)`` by parameter name, read from
+        the device table), ``max_grad_norm``, ``skipped_steps``."""
+        if not self._grouped:
+            return {"param_groups": None, "max_grad_norm": None, "skipped_steps": 0}
+        tab = self.group_table.detach().cpu().double().tolist()
+        return {"param_groups": {nm: tuple(tab[r]) for nm, r in self._group_row_of.items()},
+                "max_grad_norm": None if self.max_norm is None else float(self.max_norm.item()),
+                "skipped_steps": 0 if self.stats is None else int(self.stats[3].item())}
+
+    def _load_group_state(self, sd):
+        """Dictionaries written before these keys existed simply lack them: whatever the constructor set stays.  A
+        dictionary that carries groups or a clip loaded into an optimizer built WITHOUT them would silently train with one
+        lr and no clip: that is an error."""
+        if not self._grouped:
+            if sd.get("param_groups") is not None or sd.get("max_grad_norm") is not None:
+                raise ValueError("FlatAdamW.load_state_dict: the state was saved by an optimizer with param_groups / "
+                                 "max_grad_norm, this one was built without them -- pass them to the constructor")
+            return
+        if sd.get("max_grad_norm") is not None and self.max_norm is None:
+            raise ValueError("FlatAdamW.load_state_dict: the state carries max_grad_norm, this optimizer was built without it")
+        if sd.get("param_groups") is not None:
+            self._set_groups(groups_from_named(sd["param_groups"]))
+        if self.max_norm is not None and sd.get("max_grad_norm") is not None:
+            self.max_norm.fill_(float(sd["max_grad_norm"]))
+        if self.stats is not None and "skipped_steps" in sd:
+            self.stats[3].fill_(float(sd["skipped_steps"]))
 
     def load_state_dict(self, sd):
         ea, es = self._named_slices(self.exp_avg), self._named_slices(self.exp_avg_sq)
@@ -378,6 +531,7 @@ class FlatAdamW:
                 for n, v in self._named_slices(self.ema).items():
                     v.copy_(sd["ema"][n])
         self.betas, self.eps, self.weight_decay = tuple(sd["betas"]), sd["eps"], sd["weight_decay"]
+        self._load_group_state(sd)
 
     def ema_state_dict(self, prefix=""):
         """The EMA weights under the model's own ``state_dict`` key names (``prefix`` + name).  The reference's
@@ -393,6 +547,8 @@ class FlatAdamW:
         ``allreduce_sum_`` / ``GradExchange.finish(mean=False)``: the data-parallel mean without its own pass)."""
         f = self.flat
         f.finish_backward()         # idempotent: nothing queued in the steady state of a captured step
+        if self._grouped:
+            return self._step_groups(grad_scale)
         rc = L.lib().fv_adamw_flat(
             L.ptr(f.param_flat), L.ptr(f.grad_flat), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), L.ptr(self.ema),
             L.ptr(f.shadow_flat), L.ptr(self.decay_mask), L.ptr(self.lr), L.ptr(self.step_t),
@@ -401,6 +557,24 @@ class FlatAdamW:
             ctypes.c_size_t(f.param_flat.numel()), L.stream_of(f.param_flat))
         L.check(rc, "adamw_flat")
         f.refresh_transposed()      # (the kernel above has just re-cast the bf16 shadows)
+
+    def _step_groups(self, grad_scale):
+        """Groups / clipping / skipping: the norm launch (only when the norm is needed), then ``fv_adamw_flat_groups``."""
+        f = self.flat
+        n = f.param_flat.numel()
+        st = L.stream_of(f.param_flat)
+        if self.partials is not None:
+            rc = L.lib().fv_grad_sumsq_partials(L.ptr(f.grad_flat), L.ptr(self.partials), ctypes.c_size_t(n), st)
+            L.check(rc, "grad_sumsq_partials")
+        rc = L.lib().fv_adamw_flat_groups(
+            L.ptr(f.param_flat), L.ptr(f.grad_flat), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), L.ptr(self.ema),
+            L.ptr(f.shadow_flat), L.ptr(self.group_ids), L.ptr(self._group_table_full), L.i32(MAX_PARAM_GROUPS),
+            L.ptr(self.lr), L.ptr(self.step_t), L.ptr(self.partials),
+            L.i32(0 if self.partials is None else self.partials.numel()), L.ptr(self.max_norm), L.ptr(self.stats),
+            L.i32(self.skip_nonfinite), ctypes.c_float(self.betas[0]), ctypes.c_float(self.betas[1]),
+            ctypes.c_float(self.eps), ctypes.c_float(self.ema_decay), ctypes.c_float(grad_scale), ctypes.c_size_t(n), st)
+        L.check(rc, "adamw_flat_groups")
+        f.refresh_transposed()
 
 
 def save_checkpoint(path, model, opt, prefix="backbone.", **extra):

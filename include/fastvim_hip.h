@@ -40,7 +40,10 @@ const char* fv_last_error(void);
  *      fv_gemm_bf16_addnorm_rw(_ok), and adds fv_mixer_scan_bwd_xproj(_ok), fv_mixer_conv_pool_bwd2(_ok),
  *      fv_chunk_rows_bf16.
  *   3  round 6 adds fv_mixer_conv_pool_bwd_dgrad(_ok, _blocks), fv_transpose_bf16_batched, fv_gemm_bf16_tn_grouped_wide8
- *      (nothing removed or changed). */
+ *      (nothing removed or changed).
+ *      Later, still 3: fv_grad_sumsq_blocks, fv_grad_sumsq_partials and fv_adamw_flat_groups were ADDED (layer-wise lr
+ *      decay and global-norm gradient clipping in the fused optimizer); no existing entry point changed, so the number
+ *      stays. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -564,6 +567,38 @@ int fv_adamw_flat(float* params, const float* grads, float* exp_avg, float* exp_
                   void* shadow_bf16, const uint8_t* decay_mask, const float* lr, float* step, float beta1,
                   float beta2, float eps, float weight_decay, float ema_decay, float grad_scale, size_t n,
                   fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Fused optimizer with parameter groups and global-norm gradient clipping: the reference's fine-tune recipe
+ * (mae/lr_decay.py:param_groups_lrd groups with an lr_scale each, mae/finetune_imagenet.py:148-151, 238-262;
+ * gradient_clip_val of mae/config/finetune_FastVimH_448.yaml = torch.nn.utils.clip_grad_norm_ on the mean gradient).
+ *
+ * fv_grad_sumsq_blocks(n): host-side size query, G = number of workgroups = number of fp32 partials of the launch below,
+ *   a pure function of n (1 <= G <= 1024; never of the device).
+ * fv_grad_sumsq_partials: ONE launch; partials[b] = sum of grads[i]^2 over workgroup b's share of the RAW gradient (no
+ *   grad_scale), accumulated in a fixed order (no atomics): same input, same bits.  n % 4 == 0, grads 16-byte aligned,
+ *   partials holds G floats.
+ * fv_adamw_flat_groups: the pass of fv_adamw_flat with
+ *   group_ids    one byte per element (in place of decay_mask): row of group_table; padding elements carry 0
+ *   group_table  n_groups rows (1 <= n_groups <= 256) of two floats (lr_scale, weight_decay), DEVICE memory: element
+ *                update with lr_g = lr[0] * lr_scale, p *= 1 - lr_g * weight_decay, step size lr_g / bias_correction1
+ *   partials     NULL, or the n_partials = fv_grad_sumsq_blocks(n) floats fv_grad_sumsq_partials wrote (16-byte aligned).
+ *                Every workgroup sums them in one fixed order: total_norm = grad_scale * sqrt(sum)
+ *   max_norm     NULL, or a device scalar (needs partials): clip_coef = min(1, max_norm / (total_norm + 1e-6)) and every
+ *                gradient element is read as g * (grad_scale * clip_coef)
+ *   stats        4 floats, required with partials: [total_norm, clip_coef, finite (0/1), skipped_steps].  The first three
+ *                are written by the call; skipped_steps is a counter the call only ever increments (zero it once)
+ *   skip_nonfinite  non-zero (needs partials): when the sum of squares is not finite the call leaves params, exp_avg,
+ *                exp_avg_sq, ema, shadow and step untouched and adds 1 to skipped_steps
+ * lr, step as for fv_adamw_flat.  n % 4 == 0.
+ * ---------------------------------------------------------------------- */
+int fv_grad_sumsq_blocks(size_t n);
+int fv_grad_sumsq_partials(const float* grads, float* partials, size_t n, fv_stream_t stream);
+int fv_adamw_flat_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema,
+                         void* shadow_bf16, const uint8_t* group_ids, const float* group_table, int n_groups,
+                         const float* lr, float* step, const float* partials, int n_partials, const float* max_norm,
+                         float* stats, int skip_nonfinite, float beta1, float beta2, float eps, float ema_decay,
+                         float grad_scale, size_t n, fv_stream_t stream);
 
 #ifdef __cplusplus
 }
