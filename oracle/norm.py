@@ -14,9 +14,11 @@ import torch
 
 def fused_add_norm_oracle(x, weight, bias=None, residual=None, eps=1e-6, prenorm=False,
                           residual_in_fp32=False, is_rms_norm=True, row_scale=None,
-                          compute_dtype=torch.float64):
+                          compute_dtype=torch.float64, out_dtype=None):
     """``row_scale`` (B,) optionally scales ``x`` per sample before the add: this is
-    DropPath applied to the mixer output (models/fastvim.py:182-190, timm DropPath)."""
+    DropPath applied to the mixer output (models/fastvim.py:182-190, timm DropPath).
+    ``out_dtype`` stores ``y`` in that dtype instead of ``x.dtype`` (the cast to the mixer's
+    compute dtype folded into the store, ``layer_norm_fn(..., out_dtype=...)``)."""
     cd = compute_dtype
     xf = x.to(cd)
     if row_scale is not None:
@@ -33,5 +35,5 @@ def fused_add_norm_oracle(x, weight, bias=None, residual=None, eps=1e-6, prenorm
         y = (r - mu) * rstd * weight.to(cd)
     if bias is not None:
         y = y + bias.to(cd)
-    y = y.to(x.dtype)
+    y = y.to(x.dtype if out_dtype is None else out_dtype)
     return (y, r.to(res_dtype)) if prenorm else y
