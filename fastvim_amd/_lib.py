@@ -29,6 +29,7 @@ C_ABI_SYMBOLS = (
     "fv_column_sum", "fv_gemm_bf16_addnorm", "fv_gemm_bf16_dgrad_addnorm_blocks", "fv_gemm_bf16_dgrad_addnorm_bwd", "fv_gemm_bf16_dgrad_addnorm_bwd2", "fv_gemm_bf16_addnorm2", "fv_mixer_combine_out_proj_addnorm_ok", "fv_mixer_combine_out_proj_addnorm", "fv_gemm_f32",
     "fv_mixer_conv_pool_bwd_dgrad_ok", "fv_mixer_conv_pool_bwd_dgrad_blocks", "fv_mixer_conv_pool_bwd_dgrad", "fv_transpose_bf16_batched", "fv_gemm_bf16_tn_grouped_wide8",
     "fv_grad_sumsq_blocks", "fv_grad_sumsq_partials", "fv_adamw_flat_groups",
+    "fv_pack_weight_frags_batched", "fv_mixer_conv_pool_bwd_dgrad_pk", "fv_mixer_combine_out_proj_addnorm_pk",
 )
 
 

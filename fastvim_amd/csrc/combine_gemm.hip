@@ -11,7 +11,8 @@
 //            needs it -- and into a 64 x 384 bf16 A panel in LDS;
 //   phase 2  the panel never moves again: the K loop has no barrier and no A traffic; wave w owns output columns
 //            [48 w, 48 w + 48) and streams ITS quarter of W_out straight from L2 into MFMA operand registers (a lane's
-//            fragment is 16 contiguous bytes of one weight row), six 32-deep k steps ahead in line pairs -- the first six
+//            fragment is 16 contiguous bytes of one weight row; PK: of the fragment-major copy, where a load instruction
+//            reads 1 KiB contiguous), six 32-deep k steps ahead in line pairs -- the first six
 //            are requested at kernel entry and arrive under phase 1;
 //   phase 3  the epilogue of gemm_addnorm_kernel<64>, lane for lane: product rounded to bf16 into an LDS tile, then
 //            residual add + RMSNorm of whole 192-wide rows (the residual rows are requested at kernel entry too).
@@ -30,6 +31,9 @@ constexpr int CG_RSA = CG_K * 2 + 16;          // A panel row stride (bytes): = 
 constexpr int CG_RSB = CG_N * 2 + 16;          // product tile row stride of the add + norm epilogue (gemm_mfma.hip)
 constexpr int CG_PD = 6;                       // k steps of weight fragments in flight per wave (3: the K loop took 8 us)
 constexpr int CG_KS = CG_K / 32;               // 12 k steps
+#ifndef CG_FORCE_PK
+#define CG_FORCE_PK 0  // timing probe: the plain entry point streams its weight with the packed addressing (values are wrong)
+#endif
 #ifndef CG_DBG
 #define CG_DBG 0      // phase probes (tools/probe/r05_combine_phases.sh): 1 no gating loop, 2 no K loop, 3 no epilogue, 4 no g stores
 #endif
@@ -44,7 +48,7 @@ struct CgParams {
   float ln_eps;
   Geo geo;
   int B;
-  const bf16_t* W;         // (192, ldw) bf16, row-major: out_proj.weight
+  const bf16_t* W;         // (192, ldw) bf16, row-major: out_proj.weight; PK: its fragment-major copy (fv_pack_weight_frags_batched)
   long ldw;
   const float* residual;   // (M, 192) fp32
   const float* nw;         // (192) RMSNorm weight
@@ -60,6 +64,10 @@ struct CgParams {
 
 __device__ __forceinline__ float cg_hsum(f2 v) { return v.x + v.y; }
 
+// PK: the weight is the fragment-major copy -- 16-byte unit ((wv * 12 + ks) * 3 + nb) * 64 + lane is the fragment lane `lane`
+// of wave wv feeds the MFMAs of column block nb at k step ks: a load instruction reads 1 KiB contiguous, a wave's whole
+// stream is one 36 KB run.  Only the address of a load differs from the plain form.
+template <bool PK>
 __global__ __launch_bounds__(CG_NT, 2) void combine_out_proj_addnorm_kernel(CgParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef PairVec<bf16_t, 3> P;
@@ -86,6 +94,12 @@ __global__ __launch_bounds__(CG_NT, 2) void combine_out_proj_addnorm_kernel(CgPa
   const int fn = lane & 15, fk = lane >> 4;
   const bf16_t* wrow[3];
   cg_bf16x8 fb[CG_PD][3];
+  const char* wpk = reinterpret_cast<const char*>(p.W) + wv * (CG_KS * 3 * 1024);      // (uniform) this wave's packed stream
+  const uint32_t wpk_lane = (uint32_t)lane * 16;
+  auto wfrag = [&](int nb, int ks) {          // the weight fragment of column block nb at k step ks
+    if constexpr (PK) return *reinterpret_cast<const cg_bf16x8*>(wpk + (ks * 3 + nb) * 1024 + wpk_lane);
+    else return *reinterpret_cast<const cg_bf16x8*>(wrow[nb] + ks * 32);
+  };
   float4 ne_r[2][2][3], ne_w[3];
   float ne_sc[2][2];
   {
@@ -143,13 +157,13 @@ __global__ __launch_bounds__(CG_NT, 2) void combine_out_proj_addnorm_kernel(CgPa
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int nb = 0; nb < 3; ++nb) wrow[nb] = p.W + (long)(wv * 48 + nb * 16 + fn) * p.ldw + fk * 8;
+    for (int nb = 0; nb < 3; ++nb) wrow[nb] = PK ? nullptr : p.W + (long)(wv * 48 + nb * 16 + fn) * p.ldw + fk * 8;
 #pragma unroll
     for (int s = 0; s < CG_PD; s += 2)
 #pragma unroll
       for (int nb = 0; nb < 3; ++nb)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) fb[s + h][nb] = *reinterpret_cast<const cg_bf16x8*>(wrow[nb] + (s + h) * 32);
+        for (int h = 0; h < 2; ++h) fb[s + h][nb] = wfrag(nb, s + h);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int q = 0; q < 3; ++q) ysum[q] = ysf[q] + ysb[q];
@@ -274,7 +288,7 @@ __global__ __launch_bounds__(CG_NT, 2) void combine_out_proj_addnorm_kernel(CgPa
       for (int nb = 0; nb < 3; ++nb)
 #pragma unroll
         for (int h = 0; h < 2; ++h)
-          fb[(kp + h) % CG_PD][nb] = *reinterpret_cast<const cg_bf16x8*>(wrow[nb] + (kp + h + CG_PD) * 32);
+          fb[(kp + h) % CG_PD][nb] = wfrag(nb, kp + h + CG_PD);
     }
     // the refill stays HERE: left alone, the scheduler sinks every load to its first use (shorter live ranges) and each
     // k step then waits out a full L2 round trip
@@ -382,7 +396,7 @@ extern "C" int fv_mixer_combine_out_proj_addnorm_ok(int batch, int rows, int col
          cols > 0 && cols <= 16 && (long)batch * rows * cols * CG_K * 4 < 0x7fffffffL;      // 32-bit byte offsets into xz
 }
 
-extern "C" int fv_mixer_combine_out_proj_addnorm(const void* xz, const void* skip, const float* yc, const float* ln_w,
+static int cg_launch(bool packed, const void* xz, const void* skip, const float* yc, const float* ln_w,
                                                  const float* ln_b, float ln_eps, void* g, float* mean, float* rstd_ln,
                                                  int batch, int rows, int cols, int tok_stride_row, int tok_stride_col,
                                                  const void* W, long ldw, const float* residual,
@@ -398,6 +412,7 @@ extern "C" int fv_mixer_combine_out_proj_addnorm(const void* xz, const void* ski
            "mixer_combine_out_proj_addnorm: token strides (%d,%d) are neither row-major nor transposed for a %dx%d grid",
            tok_stride_row, tok_stride_col, rows, cols);
   FV_CHECK(((uintptr_t)W & 15) == 0 && ldw % 8 == 0 && ldw >= CG_K, "mixer_combine_out_proj_addnorm: weight rows must be 16-byte aligned");
+  FV_CHECK(!packed || ldw == CG_K, "mixer_combine_out_proj_addnorm_pk: the packed weight has no row padding (ldw = %d)", CG_K);
   FV_CHECK(((uintptr_t)residual & 15) == 0 && ((uintptr_t)residual_out & 15) == 0 && ((uintptr_t)y & 7) == 0 &&
                ((uintptr_t)norm_weight & 15) == 0, "mixer_combine_out_proj_addnorm: row operands must be 16-byte aligned");
   FV_CHECK(!row_scale || rows_per_scale > 0, "mixer_combine_out_proj_addnorm: rows_per_scale must be positive");
@@ -411,7 +426,23 @@ extern "C" int fv_mixer_combine_out_proj_addnorm(const void* xz, const void* ski
   p.M = batch * rows * cols;
   p.d_in = CG_K;
   const size_t smem = (size_t)CG_BM * CG_RSA;
-  hipLaunchKernelGGL(combine_out_proj_addnorm_kernel, dim3(batch * fv_cdiv(rows, 4)), dim3(CG_NT), smem, (hipStream_t)stream, p);
+  const dim3 grid(batch * fv_cdiv(rows, 4)), block(CG_NT);
+  if (packed || CG_FORCE_PK) hipLaunchKernelGGL(combine_out_proj_addnorm_kernel<true>, grid, block, smem, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(combine_out_proj_addnorm_kernel<false>, grid, block, smem, (hipStream_t)stream, p);
   FV_LAUNCH_CHECK();
   return FV_OK;
 }
+
+#define CG_ARGS_DECL                                                                                                          \
+  const void *xz, const void *skip, const float *yc, const float *ln_w, const float *ln_b, float ln_eps, void *g,             \
+      float *mean, float *rstd_ln, int batch, int rows, int cols, int tok_stride_row, int tok_stride_col, const void *W,      \
+      long ldw, const float *residual, const float *norm_weight, const float *row_scale, int rows_per_scale, void *y,         \
+      float *residual_out, float *rstd, float eps, fv_stream_t stream
+#define CG_ARGS                                                                                                               \
+  xz, skip, yc, ln_w, ln_b, ln_eps, g, mean, rstd_ln, batch, rows, cols, tok_stride_row, tok_stride_col, W, ldw, residual,    \
+      norm_weight, row_scale, rows_per_scale, y, residual_out, rstd, eps, stream
+
+extern "C" int fv_mixer_combine_out_proj_addnorm(CG_ARGS_DECL) { return cg_launch(false, CG_ARGS); }
+
+// W is the fragment-major copy of out_proj.weight (fv_pack_weight_frags_batched, K = 384); ldw must be 384
+extern "C" int fv_mixer_combine_out_proj_addnorm_pk(CG_ARGS_DECL) { return cg_launch(true, CG_ARGS); }

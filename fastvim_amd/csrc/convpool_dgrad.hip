@@ -16,7 +16,7 @@
 //            (two barriers) and leave as one partial row per workgroup;
 //   phase 2  C (64 x 192) = [panel | z half of d xz] @ W_in: wave w owns output columns [48 w, 48 w + 48) and streams its
 //            quarter of the TRANSPOSED weight (192 x 768, K-contiguous: a lane's MFMA fragment is 16 contiguous bytes)
-//            from L2 straight into operand registers; the x half has no barrier and no A traffic, the z half -- written by
+//            from L2 straight into operand registers (PK: from its fragment-major copy, 1 KiB per load instruction); the x half has no barrier and no A traffic, the z half -- written by
 //            combine_bwd, read here for the only time -- comes through a three-stage LDS-DMA ring whose first stages
 //            are requested before the K loop;
 //   phase 3  gemm_dgrad_addnorm_bwd_kernel<64>'s epilogue from the product tile on, lane for lane (d hidden and d residual
@@ -52,6 +52,9 @@ constexpr int CD_O_B = (CD_BM * CD_RSB + 255) / 256 * 256, CD_O_S = CD_O_B + 2 *
 constexpr int CD_SMEM = CD_O_S + 4 * 32 * (64 * 2 + 16);                                           // 76 800
 static_assert(CD_O_RING + 3 * CD_ZST <= CD_SMEM && CD_O_RING + 4 * CD_SLOT * 4 <= CD_SMEM, "LDS regions");
 static_assert(2 * CD_SMEM <= 160 * 1024, "two workgroups per CU");
+#ifndef CD_FORCE_PK
+#define CD_FORCE_PK 0  // timing probe: the plain entry point streams its weight with the packed addressing (values are wrong)
+#endif
 #ifndef CD_DBG
 #define CD_DBG 0      // phase probes (tuning): 1 no conv arithmetic, 2 no K loop, 3 no epilogue, 4 no second phase
 #endif
@@ -69,7 +72,7 @@ struct CdParams {
   Geo geo;
   int B;
   // ---- in_proj data gradient + norm adjoint (NormEpi of fv_gemm_bf16_dgrad_addnorm_bwd2)
-  const bf16_t* Wt;        // (192, ldwt) bf16: in_proj.weight^T, K-contiguous
+  const bf16_t* Wt;        // (192, ldwt) bf16: in_proj.weight^T, K-contiguous; PK: its fragment-major copy (fv_pack_weight_frags_batched)
   long ldwt;
   const float* dres_out;   // (M, 192) fp32 gradient of the residual stream from above, nullable
   const float* r;          // (M, 192) fp32 saved normalisation input
@@ -104,7 +107,10 @@ constexpr int cd_younger(int t) {
 }
 static_assert(cd_younger(3) < 64 && cd_younger(4) < 64 && cd_younger(5) < 64, "vmcnt is a 6-bit counter");
 
-template <int NT, bool X2>
+// PK: the weight is the fragment-major copy -- 16-byte unit ((wv * 24 + ks) * 3 + nb) * 64 + lane is the fragment lane `lane`
+// of wave wv feeds the MFMAs of column block nb at k step ks, so a load instruction reads 1 KiB contiguous and a wave's whole
+// stream is one 72 KB run.  Only the address of a load differs from the plain form.
+template <int NT, bool X2, bool PK>
 __global__ __launch_bounds__(CD_NT, 2) void conv_pool_bwd_dgrad_kernel(CdParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef PairVec<bf16_t, 1> P;
@@ -309,7 +315,13 @@ __global__ __launch_bounds__(CD_NT, 2) void conv_pool_bwd_dgrad_kernel(CdParams 
   const bf16_t* wrow[3];
   bf16x8 fb[CD_PD][3];
 #pragma unroll
-  for (int nb = 0; nb < 3; ++nb) wrow[nb] = p.Wt + (long)(wv * 48 + nb * 16 + fn) * p.ldwt + fk * 8;
+  for (int nb = 0; nb < 3; ++nb) wrow[nb] = PK ? nullptr : p.Wt + (long)(wv * 48 + nb * 16 + fn) * p.ldwt + fk * 8;
+  const char* wpk = reinterpret_cast<const char*>(p.Wt) + wv * (CD_KS * 3 * 1024);     // (uniform) this wave's packed stream
+  const uint32_t wpk_lane = (uint32_t)lane * 16;
+  auto wfrag = [&](int nb, int ks) {          // the weight fragment of column block nb at k step ks
+    if constexpr (PK) return *reinterpret_cast<const bf16x8*>(wpk + (ks * 3 + nb) * 1024 + wpk_lane);
+    else return *reinterpret_cast<const bf16x8*>(wrow[nb] + ks * 32);
+  };
   // z ring: this thread's two 16-byte pieces of a stage (physical slot e = tid + 256 i -> row e >> 3, chunk (e & 7) ^ (row & 7))
   uint32_t zoff[2];
   const uint32_t ring = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)(smem + CD_O_RING);
@@ -332,7 +344,7 @@ __global__ __launch_bounds__(CD_NT, 2) void conv_pool_bwd_dgrad_kernel(CdParams 
 #pragma unroll
     for (int nb = 0; nb < 3; ++nb)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) fb[s + h][nb] = *reinterpret_cast<const bf16x8*>(wrow[nb] + (s + h) * 32);
+      for (int h = 0; h < 2; ++h) fb[s + h][nb] = wfrag(nb, s + h);
   __builtin_amdgcn_sched_barrier(0);
   // the saved normalisation rows of the epilogue (lane mapping of add_norm_bwd3_kernel<16>): requested here, they arrive
   // under the K loop
@@ -381,7 +393,7 @@ __global__ __launch_bounds__(CD_NT, 2) void conv_pool_bwd_dgrad_kernel(CdParams 
       for (int nb = 0; nb < 3; ++nb)
 #pragma unroll
         for (int h = 0; h < 2; ++h)
-          fb[(kp + h) % CD_PD][nb] = *reinterpret_cast<const bf16x8*>(wrow[nb] + (kp + h + CD_PD) * 32);
+          fb[(kp + h) % CD_PD][nb] = wfrag(nb, kp + h + CD_PD);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -549,8 +561,8 @@ extern "C" int fv_mixer_conv_pool_bwd_dgrad_ok(int batch, int rows, int cols, in
 
 extern "C" int fv_mixer_conv_pool_bwd_dgrad_blocks(int batch, int rows) { return batch * fv_cdiv(rows, 4); }
 
-extern "C" int fv_mixer_conv_pool_bwd_dgrad(
-    const void* xz, const void* dskip, const float* dxc, const void* dxc2, const float* conv_w, const float* conv_b,
+static int cd_launch(
+    bool packed, const void* xz, const void* dskip, const float* dxc, const void* dxc2, const float* conv_w, const float* conv_b,
     const float* conv_w_b, const float* conv_b_b, const float* D, const float* D_b, void* dxz, float* conv_partials, int batch,
     int rows, int cols, int tok_stride_row, int tok_stride_col, float scaling, const void* W_in_t, long ldwt,
     const float* dresidual_out, const float* r, const float* rstd, const float* norm_weight, const float* row_scale,
@@ -564,6 +576,7 @@ extern "C" int fv_mixer_conv_pool_bwd_dgrad(
            "mixer_conv_pool_bwd_dgrad: token strides (%d,%d) are neither row-major nor transposed for a %dx%d grid",
            tok_stride_row, tok_stride_col, rows, cols);
   FV_CHECK(((uintptr_t)W_in_t & 15) == 0 && ldwt % 8 == 0 && ldwt >= CD_K, "mixer_conv_pool_bwd_dgrad: transposed weight rows must be 16-byte aligned");
+  FV_CHECK(!packed || ldwt == CD_K, "mixer_conv_pool_bwd_dgrad_pk: the packed weight has no row padding (ldwt = %d)", CD_K);
   FV_CHECK(((uintptr_t)r & 15) == 0 && ((uintptr_t)dresidual_in & 15) == 0 && ((uintptr_t)dx & 7) == 0 &&
                ((uintptr_t)norm_weight & 15) == 0 && ((uintptr_t)dresidual_out & 15) == 0 && ((uintptr_t)dxz & 15) == 0,
            "mixer_conv_pool_bwd_dgrad: row operands must be 16-byte aligned");
@@ -581,16 +594,35 @@ extern "C" int fv_mixer_conv_pool_bwd_dgrad(
   p.dres_in = dresidual_in; p.pw = partial_dw; p.W2 = (const bf16_t*)W2; p.ldw2 = ldw2; p.C2 = (bf16_t*)C2; p.N2 = N2;
   p.M = batch * rows * cols;
   const dim3 grid(batch * fv_cdiv(rows, 4)), block(CD_NT);
-#define FV_CD(NTT, XX)                                                                                              \
+#define FV_CD(NTT, XX, PP)                                                                                          \
   do {                                                                                                              \
     static FvOncePerDevice done;                                                                                    \
     if (done.first())                                                                                               \
-      (void)hipFuncSetAttribute((const void*)conv_pool_bwd_dgrad_kernel<NTT, XX>, hipFuncAttributeMaxDynamicSharedMemorySize, CD_SMEM); \
-    hipLaunchKernelGGL((conv_pool_bwd_dgrad_kernel<NTT, XX>), grid, block, CD_SMEM, (hipStream_t)stream, p);        \
+      (void)hipFuncSetAttribute((const void*)conv_pool_bwd_dgrad_kernel<NTT, XX, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, CD_SMEM); \
+    hipLaunchKernelGGL((conv_pool_bwd_dgrad_kernel<NTT, XX, PP>), grid, block, CD_SMEM, (hipStream_t)stream, p);    \
   } while (0)
-  if (cols == 14) { if (dxc2) FV_CD(14, true); else FV_CD(14, false); }
-  else { if (dxc2) FV_CD(16, true); else FV_CD(16, false); }
+#define FV_CD2(NTT, XX) do { if (packed || CD_FORCE_PK) FV_CD(NTT, XX, true); else FV_CD(NTT, XX, false); } while (0)
+  if (cols == 14) { if (dxc2) FV_CD2(14, true); else FV_CD2(14, false); }
+  else { if (dxc2) FV_CD2(16, true); else FV_CD2(16, false); }
+#undef FV_CD2
 #undef FV_CD
   FV_LAUNCH_CHECK();
   return FV_OK;
 }
+
+#define CD_ARGS_DECL                                                                                                          \
+  const void *xz, const void *dskip, const float *dxc, const void *dxc2, const float *conv_w, const float *conv_b,            \
+      const float *conv_w_b, const float *conv_b_b, const float *D, const float *D_b, void *dxz, float *conv_partials,        \
+      int batch, int rows, int cols, int tok_stride_row, int tok_stride_col, float scaling, const void *W_in_t, long ldwt,    \
+      const float *dresidual_out, const float *r, const float *rstd, const float *norm_weight, const float *row_scale,        \
+      int rows_per_scale, void *dx, float *dresidual_in, float *partial_dw, const void *W2, void *C2, int N2, long ldw2,      \
+      fv_stream_t stream
+#define CD_ARGS                                                                                                               \
+  xz, dskip, dxc, dxc2, conv_w, conv_b, conv_w_b, conv_b_b, D, D_b, dxz, conv_partials, batch, rows, cols, tok_stride_row,    \
+      tok_stride_col, scaling, W_in_t, ldwt, dresidual_out, r, rstd, norm_weight, row_scale, rows_per_scale, dx,              \
+      dresidual_in, partial_dw, W2, C2, N2, ldw2, stream
+
+extern "C" int fv_mixer_conv_pool_bwd_dgrad(CD_ARGS_DECL) { return cd_launch(false, CD_ARGS); }
+
+// W_in_t is the fragment-major copy of in_proj.weight^T (fv_pack_weight_frags_batched, K = 768); ldwt must be 768
+extern "C" int fv_mixer_conv_pool_bwd_dgrad_pk(CD_ARGS_DECL) { return cd_launch(true, CD_ARGS); }

@@ -194,6 +194,26 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(TransposeJobs J) {
   }
 }
 
+
+// Fragment-major copies of up to 64 weights (192, K), K-contiguous, in one launch: the 16-byte unit
+//   u = ((wv * K / 32 + ks) * 3 + nb) * 64 + lane   holds   src[48 wv + 16 nb + (lane & 15)][32 ks + 8 (lane >> 4) .. + 8)
+// -- the MFMA operand lane `lane` of wave wv loads for column block nb at k step ks in fv_mixer_conv_pool_bwd_dgrad_pk
+// (K = 768) and fv_mixer_combine_out_proj_addnorm_pk (K = 384); fastvim_amd.mixer_ops.pack_index is the same map.  A thread
+// moves one unit: the writes are contiguous, the reads half lines of 16 rows.
+constexpr int PKW_ROWS = 192;
+struct PackJobs {
+  const uint4* src[TRJ_MAX];
+  uint4* dst[TRJ_MAX];
+  int ks_n;      // K / 32
+};
+__global__ __launch_bounds__(256) void pack_weight_frags_kernel(PackJobs J) {
+  const int u = blockIdx.x * 256 + threadIdx.x;
+  if (u >= PKW_ROWS * J.ks_n * 4) return;
+  const int lane = u & 63, t = u >> 6, nb = t % 3, ks = (t / 3) % J.ks_n, wv = t / (3 * J.ks_n);
+  const int row = 48 * wv + 16 * nb + (lane & 15), unit_in_row = 4 * ks + (lane >> 4);
+  J.dst[blockIdx.y][u] = J.src[blockIdx.y][row * (J.ks_n * 4) + unit_in_row];
+}
+
 }  // namespace
 
 extern "C" int fv_patch_unfold(const void* img, int img_dtype, void* out, int out_dtype, int batch, int chans, int height,
@@ -290,6 +310,22 @@ extern "C" int fv_transpose_bf16_batched(const void* const* srcs, void* const* d
   }
   J.rows = rows; J.cols = cols;
   hipLaunchKernelGGL(transpose_bf16_kernel, dim3(fv_cdiv(cols, 32), fv_cdiv(rows, 32), njobs), dim3(256), 0, (hipStream_t)stream, J);
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
+extern "C" int fv_pack_weight_frags_batched(const void* const* srcs, void* const* dsts, int njobs, int K, fv_stream_t stream) {
+  FV_CHECK(srcs && dsts && njobs > 0 && njobs <= TRJ_MAX, "pack_weight_frags_batched: 1..%d jobs", TRJ_MAX);
+  FV_CHECK(K == 384 || K == 768, "pack_weight_frags_batched: K = %d is not a built reduction length (384, 768)", K);
+  PackJobs J{};
+  for (int j = 0; j < njobs; ++j) {
+    FV_CHECK(srcs[j] && dsts[j] && srcs[j] != dsts[j], "pack_weight_frags_batched: null or aliased pointer in job %d", j);
+    FV_CHECK(((uintptr_t)srcs[j] & 15) == 0 && ((uintptr_t)dsts[j] & 15) == 0, "pack_weight_frags_batched: job %d is not 16-byte aligned", j);
+    J.src[j] = (const uint4*)srcs[j];
+    J.dst[j] = (uint4*)dsts[j];
+  }
+  J.ks_n = K / 32;
+  hipLaunchKernelGGL(pack_weight_frags_kernel, dim3(fv_cdiv(PKW_ROWS * J.ks_n * 4, 256), njobs), dim3(256), 0, (hipStream_t)stream, J);
   FV_LAUNCH_CHECK();
   return FV_OK;
 }

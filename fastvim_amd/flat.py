@@ -36,6 +36,22 @@ _MIXER_GROUPS = (
 )
 
 
+def _drop_derived_shadows(model):
+    """Delete the transposed and fragment-major shadows (and their version stamps) a flat training state hung on the
+    model's parameters and mixers: a state that is closed, or one attached after another, must never have the previous
+    state's copies read in its place (the fused optimizer does not bump ``_version``, so the version check alone would
+    not catch them)."""
+    for p in model.parameters():
+        for a in ("_fv_shadow_t", "_fv_shadow_t_version", "_fv_shadow_pk", "_fv_shadow_pk_version"):
+            if hasattr(p, a):
+                delattr(p, a)
+    for mod in model.modules():
+        fv = mod.__dict__.get("_fv")
+        if isinstance(fv, dict):
+            fv.pop("Wx2_shadow_t", None)
+            fv.pop("Wx2_t_params", None)
+
+
 class FlatTrainingState:
     def __init__(self, model, shadow_dtype=torch.bfloat16, process_group=None, comm_dtype=None,
                  chunk_bytes=256 << 20):
@@ -45,6 +61,8 @@ class FlatTrainingState:
         self.group = process_group
         self.comm_dtype = comm_dtype
         self.chunk = max(1, chunk_bytes // 4)
+        self._model = model
+        _drop_derived_shadows(model)
         named = dict(model.named_parameters())
         # Layer-major layout: [parameters before the block stack | block 0 | block 1 | ... | parameters after it], so
         # that the gradient of a run of blocks is ONE contiguous slice -- a bucket of the overlapped gradient exchange
@@ -151,6 +169,18 @@ class FlatTrainingState:
                     self._t_src.append(w._fv_shadow)
                     self._t_dst.append(wt)
                     self._t_params.append(w)
+        # fragment-major copies of those transposed in_proj shadows and of the out_proj shadows (192, 384): the two fused
+        # launches stream them 1 KiB per load instruction (mixer_ops.pack_index); re-made by one launch per shape after
+        # the transposes.  (source, copy, parameter) per shape
+        self._pk_jobs = {768: ([], [], []), 384: ([], [], [])}
+        if shadow_dtype == torch.bfloat16 and dev.type == "cuda":
+            for w, wt in zip(self._t_params, self._t_dst):
+                self._add_packed(768, w, wt)
+            for mod in mixers.values():
+                w = getattr(getattr(mod, "out_proj", None), "weight", None)
+                if w is not None and tuple(w.shape) == (192, 384) and w.requires_grad and getattr(w, "_fv_shadow", None) is not None:
+                    self._add_packed(384, w, w._fv_shadow)
+        self._pk_dst = self._pk_jobs[768][1] + self._pk_jobs[384][1]
         # ... and of the x_proj weight pairs of the wide models (d_inner >= 768), (2, W, d_inner) -> (2, d_inner, W): the
         # x_proj adjoint's data half streams them K-contiguous into the bf16 matrix cores (fv_mixer_xproj_bwd3)
         self._tx_src, self._tx_dst, self._tx_params = [], [], []
@@ -188,6 +218,15 @@ class FlatTrainingState:
         # after the last block unless a caller switches them on)
         _SideStream.enabled = False
 
+    def _add_packed(self, K, w, src):
+        pk = torch.empty(192 * K, device=src.device, dtype=src.dtype)
+        w._fv_shadow_pk = pk
+        w._fv_shadow_pk_version = -1
+        srcs, dsts, params = self._pk_jobs[K]
+        srcs.append(src)
+        dsts.append(pk)
+        params.append(w)
+
     def close(self):
         """Issue whatever is queued and restore the wrappers' process-wide switches (deferred reductions, grouped weight
         gradients, side stream) to what they were before this training state was attached.  Also the exit of
@@ -201,6 +240,7 @@ class FlatTrainingState:
         _SideStream.enabled = s_
         self._hook.remove()
         self._saved_switches = None
+        _drop_derived_shadows(self._model)
 
     def __enter__(self):
         return self
@@ -243,15 +283,21 @@ class FlatTrainingState:
         self.refresh_transposed()
 
     def refresh_transposed(self):
-        """Re-make the transposed in_proj shadows from ``shadow_flat`` (one launch; called after every shadow refresh:
-        here and by the fused optimizer step)."""
-        from .mixer_ops import transpose_bf16_batched
+        """Re-make the transposed in_proj shadows from ``shadow_flat`` (one launch) and then the fragment-major copies of
+        them and of the out_proj shadows (one launch per shape); called after every shadow refresh: here and by the fused
+        optimizer step."""
+        from .mixer_ops import pack_weight_frags, transpose_bf16_batched
         for src, dst, params in ((self._t_src, self._t_dst, self._t_params),
                                  (getattr(self, "_tx_src", []), getattr(self, "_tx_dst", []), getattr(self, "_tx_params", []))):
             if src:
                 transpose_bf16_batched(src, dst)
                 for p in params:
                     p._fv_shadow_t_version = p._version
+        for srcs, dsts, params in getattr(self, "_pk_jobs", {}).values():
+            if srcs:
+                pack_weight_frags(srcs, dsts)
+                for p in params:
+                    p._fv_shadow_pk_version = p._version
 
     @property
     def world_size(self):

@@ -50,6 +50,36 @@ def _shadow_t(w, cdt):
     return _shadow(w, cdt).t().contiguous()
 
 
+class _PackedWeights:
+    enabled = True      # ``use_packed_weights``
+
+
+def use_packed_weights(on):
+    """Switch the fragment-major weight path of the two fused launches on or off (default on; results are bit-identical
+    either way -- an A/B and test switch).  Returns the previous setting."""
+    was = _PackedWeights.enabled
+    _PackedWeights.enabled = bool(on)
+    return was
+
+
+def _shadow_pk(w, cdt, plain):
+    """The FRAGMENT-MAJOR compute-dtype copy FlatTrainingState keeps of an eligible weight (in_proj.weight^T, out_proj.weight:
+    ``mixer_ops.pack_index``), or None when there is none or it is switched off: the caller then takes the plain weight,
+    exactly as without a flat training state.  ``plain`` is the current plain copy it is a permutation of (``_shadow_t`` /
+    ``_shadow`` of the same weight, already refreshed): an in-place write to the parameter since the state last re-made the
+    copy (version counter) is caught here and the copy re-packed from it, like ``_shadow_t``."""
+    pk = getattr(w, "_fv_shadow_pk", None)
+    if pk is None or pk.dtype != cdt or not _PackedWeights.enabled:
+        return None
+    if w._version != w._fv_shadow_pk_version:
+        if not (plain.is_contiguous() and plain.numel() == pk.numel()):
+            return None
+        with torch.no_grad():
+            M.pack_weight_frags([plain], [pk])
+        w._fv_shadow_pk_version = w._version
+    return pk
+
+
 def _wx2_shadow_t(fv):
     """The transposed bf16 shadow (2, d_inner, W) of a mixer's x_proj weight pair kept by FlatTrainingState for the wide
     models, or None.  Re-made by the flat state after every optimizer step; an in-place write to either weight since then
@@ -387,7 +417,8 @@ def _out_proj_add_norm_fwd(g, W_out, residual, norm_w, eps, row_scale, cdt, W_in
         if xz is None and W_out_c.stride(1) == 1 and W_out_c.stride(0) % 8 == 0 and W_out_c.data_ptr() % 16 == 0:
             y, res_out, rstd = M.combine_out_proj_addnorm(pack["xz"], pack["skip"], pack["yc"], pack["ln_w"], pack["ln_b"],
                                                           pack["eps"], pack["rows"], pack["cols"], pack["transposed"],
-                                                          pack["out"], W_out_c, res2, w32, row_scale, rows_per_scale, eps)
+                                                          pack["out"], W_out_c, res2, w32, row_scale, rows_per_scale, eps,
+                                                          W_out_pk=_shadow_pk(W_out, cdt, W_out_c))
             return y, res_out, rstd, w32, row_scale, rows_per_scale
         resolve_combine(pack)
     rc = lib.fv_gemm_bf16_addnorm2(
@@ -499,7 +530,7 @@ class ChainedBlockFn(torch.autograd.Function):
             W_in_t = _shadow_t(ctx.W_in, cdt)                # (held across the launch, see _out_proj_add_norm_fwd)
             p2, dx, dres_in, pw, nb, dg_prev = M.conv_pool_bwd_dgrad(
                 xz, d_o, dxc, dxc2, cw2, cb, cwb2, cb_b, D, D_b, dxz, rows, cols, transposed, scaling, W_in_t, gg, r, rstd,
-                w32, row_scale, ctx.rows_per_scale, W2=W2, conv_grad_out=conv_grad_out)
+                w32, row_scale, ctx.rows_per_scale, W2=W2, conv_grad_out=conv_grad_out, W_in_pk=_shadow_pk(ctx.W_in, cdt, W_in_t))
             out.update(dx=dx, dres_in=dres_in, pw=pw, nb=nb, dg_prev=dg_prev)
             return p2
 

@@ -209,10 +209,11 @@ def combine_out_proj_addnorm_ok(xz, rows, cols, tpp, d_model):
 
 
 def combine_out_proj_addnorm(xz, skip, yc, ln_w, ln_b, ln_eps, rows, cols, transposed, out, W_out_c, residual2, norm_w32,
-                             row_scale, rows_per_scale, eps):
+                             row_scale, rows_per_scale, eps, W_out_pk=None):
     """``combine_fwd`` into the buffers ``out`` = (g, mean, rstd) AND out_proj + DropPath scale + residual add + RMSNorm
     of the result (``fv_gemm_bf16_addnorm``) in one launch; returns (normed (M, d) bf16, residual_out (M, d) fp32,
-    rstd (M))."""
+    rstd (M)).  ``W_out_pk``: the fragment-major copy of ``W_out_c`` (``pack_weight_frags``) -- the weight stream then
+    reads 1 KiB per load instruction; the results are bit-identical."""
     B, Ltok, two_d = xz.shape
     d = W_out_c.shape[0]
     Mrows = B * Ltok
@@ -221,9 +222,14 @@ def combine_out_proj_addnorm(xz, skip, yc, ln_w, ln_b, ln_eps, rows, cols, trans
     y = torch.empty(Mrows, d, device=xz.device, dtype=torch.bfloat16)
     res_out = torch.empty(Mrows, d, device=xz.device, dtype=torch.float32)
     rstd = torch.empty(Mrows, device=xz.device, dtype=torch.float32)
-    rc = L.lib().fv_mixer_combine_out_proj_addnorm(
+    if W_out_pk is not None:
+        assert W_out_pk.dtype == torch.bfloat16 and W_out_pk.is_contiguous() and W_out_pk.numel() == d * (two_d // 2)
+        fn, W_arg, ldw = L.lib().fv_mixer_combine_out_proj_addnorm_pk, W_out_pk, two_d // 2
+    else:
+        fn, W_arg, ldw = L.lib().fv_mixer_combine_out_proj_addnorm, W_out_c, W_out_c.stride(0)
+    rc = fn(
         L.ptr(xz), L.ptr(skip), L.ptr(yc), L.ptr(ln_w), L.ptr(ln_b), f32(ln_eps), L.ptr(g), L.ptr(mean), L.ptr(rstd_ln),
-        L.i32(B), L.i32(rows), L.i32(cols), L.i32(s_i), L.i32(s_j), L.ptr(W_out_c), ctypes.c_long(W_out_c.stride(0)),
+        L.i32(B), L.i32(rows), L.i32(cols), L.i32(s_i), L.i32(s_j), L.ptr(W_arg), ctypes.c_long(ldw),
         L.ptr(residual2), L.ptr(norm_w32), L.ptr(row_scale), L.i32(rows_per_scale), L.ptr(y), L.ptr(res_out), L.ptr(rstd),
         f32(eps), L.stream_of(xz))
     L.check(rc, "mixer_combine_out_proj_addnorm")
@@ -383,11 +389,13 @@ def conv_pool_bwd_dgrad_ok(xz, rows, cols, tpp, d_model, pool_max):
 
 
 def conv_pool_bwd_dgrad(xz, d_o, dxc, dxc2, conv_w, conv_b, conv_w_b, conv_b_b, D, D_b, dxz, rows, cols, transposed, scaling,
-                        W_in_t, dres_out, r, rstd, norm_w32, row_scale, rows_per_scale, W2=None, conv_grad_out=None):
+                        W_in_t, dres_out, r, rstd, norm_w32, row_scale, rows_per_scale, W2=None, conv_grad_out=None,
+                        W_in_pk=None):
     """``conv_pool_bwd`` (x half of ``dxz`` written, its z half read) AND ``fv_gemm_bf16_dgrad_addnorm_bwd2`` on the result in
     one launch (fv_mixer_conv_pool_bwd_dgrad).  ``W_in_t`` (d, 2 d_in) bf16 = in_proj.weight^T.  Returns
     (conv parameter-gradient sums or None when accumulated into ``conv_grad_out``, dx (M, d) bf16, dres_in (M, d) fp32,
-    pw (nb, d) partial sums of the norm weight's gradient, nb, dg_prev (M, N2) bf16 or None)."""
+    pw (nb, d) partial sums of the norm weight's gradient, nb, dg_prev (M, N2) bf16 or None).  ``W_in_pk``: the
+    fragment-major copy of ``W_in_t`` (``pack_weight_frags``); every output stays bit-identical."""
     B, Ltok, two_d = xz.shape
     d_in = two_d // 2
     d = W_in_t.shape[0]
@@ -404,10 +412,15 @@ def conv_pool_bwd_dgrad(xz, d_o, dxc, dxc2, conv_w, conv_b, conv_w_b, conv_b_b, 
     dg_prev = torch.empty(Mrows, N2, device=dev, dtype=torch.bfloat16) if W2 is not None else None
     assert dxc2 is None or (dxc2.dtype == xz.dtype and dxc2.shape == dxc.shape and dxc2.is_contiguous())
     assert W_in_t.dtype == torch.bfloat16 and W_in_t.stride(1) == 1 and W_in_t.shape[1] == two_d
-    rc = lib.fv_mixer_conv_pool_bwd_dgrad(
+    if W_in_pk is not None:
+        assert W_in_pk.dtype == torch.bfloat16 and W_in_pk.is_contiguous() and W_in_pk.numel() == d * two_d
+        fn, W_arg, ldwt = lib.fv_mixer_conv_pool_bwd_dgrad_pk, W_in_pk, two_d
+    else:
+        fn, W_arg, ldwt = lib.fv_mixer_conv_pool_bwd_dgrad, W_in_t, W_in_t.stride(0)
+    rc = fn(
         L.ptr(xz), L.ptr(d_o), L.ptr(dxc), L.ptr(dxc2), L.ptr(conv_w), L.ptr(conv_b), L.ptr(conv_w_b), L.ptr(conv_b_b),
         L.ptr(D), L.ptr(D_b), L.ptr(dxz), L.ptr(part), L.i32(B), L.i32(rows), L.i32(cols), L.i32(s_i), L.i32(s_j),
-        f32(scaling), L.ptr(W_in_t), ctypes.c_long(W_in_t.stride(0)), L.ptr(dres_out), L.ptr(r), L.ptr(rstd), L.ptr(norm_w32),
+        f32(scaling), L.ptr(W_arg), ctypes.c_long(ldwt), L.ptr(dres_out), L.ptr(r), L.ptr(rstd), L.ptr(norm_w32),
         L.ptr(row_scale), L.i32(rows_per_scale), L.ptr(dx), L.ptr(dres_in), L.ptr(pw), L.ptr(W2), L.ptr(dg_prev), L.i32(N2),
         ctypes.c_long(W2.stride(0) if W2 is not None else 0), L.stream_of(xz))
     L.check(rc, "mixer_conv_pool_bwd_dgrad")
@@ -431,6 +444,47 @@ def transpose_bf16_batched(srcs, dsts):
         ins = (ctypes.c_void_p * k)(*[t.data_ptr() for t in a])
         outs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in b])
         L.check(lib.fv_transpose_bf16_batched(ins, outs, L.i32(k), L.i32(rows), L.i32(cols), L.stream_of(a[0])), "transpose_bf16_batched")
+
+
+PACK_ROWS = 192      # output columns of the two fused projections: four waves x three 16-column MFMA blocks
+
+
+def pack_index(K):
+    """The fragment-major weight layout of the ``_pk`` launches, as a gather: a (192 * K / 8, 2) int64 tensor whose row
+    ``u`` is (row, first column) of the 8-element, 16-byte unit that packed unit ``u`` holds, for a weight (192, K) with K
+    contiguous:   u = ((wv * K / 32 + ks) * 3 + nb) * 64 + lane   holds   W[48 wv + 16 nb + (lane & 15)][32 ks + 8 (lane >> 4) .. + 8)
+    -- the MFMA operand that lane loads for column block ``nb`` at k step ``ks`` in wave ``wv``."""
+    assert K % 32 == 0
+    KS = K // 32
+    u = torch.arange(PACK_ROWS * K // 8)
+    lane, t = u % 64, u // 64
+    nb, ks, wv = t % 3, (t // 3) % KS, t // (3 * KS)
+    return torch.stack([48 * wv + 16 * nb + (lane % 16), 32 * ks + 8 * (lane // 16)], dim=1)
+
+
+def pack_weight_frags_ref(W):
+    """``pack_index`` applied with torch indexing (any device): the definition ``pack_weight_frags`` is tested against."""
+    rows, K = W.shape
+    assert rows == PACK_ROWS
+    idx = pack_index(K).to(W.device)
+    cols = idx[:, 1:2] + torch.arange(8, device=W.device)
+    return W[idx[:, 0:1], cols].reshape(rows, K)
+
+
+def pack_weight_frags(srcs, dsts):
+    """dsts[j] = fragment-major copy of srcs[j] ((192, K) bf16 contiguous, K 384 or 768; ``pack_index``), one launch per
+    64 weights (fv_pack_weight_frags_batched)."""
+    lib = L.lib()
+    rows, K = srcs[0].shape
+    for lo in range(0, len(srcs), 64):
+        a, b = srcs[lo:lo + 64], dsts[lo:lo + 64]
+        assert all(t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (rows, K) for t in a)
+        assert all(t.dtype == torch.bfloat16 and t.is_contiguous() and t.numel() == rows * K for t in b)
+        assert rows == PACK_ROWS
+        k = len(a)
+        ins = (ctypes.c_void_p * k)(*[t.data_ptr() for t in a])
+        outs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in b])
+        L.check(lib.fv_pack_weight_frags_batched(ins, outs, L.i32(k), L.i32(K), L.stream_of(a[0])), "pack_weight_frags_batched")
 
 
 XPROJ_WIDTHS = (44, 56, 80, 96, 112, 34, 36, 38, 64)

@@ -43,7 +43,10 @@ const char* fv_last_error(void);
  *      (nothing removed or changed).
  *      Later, still 3: fv_grad_sumsq_blocks, fv_grad_sumsq_partials and fv_adamw_flat_groups were ADDED (layer-wise lr
  *      decay and global-norm gradient clipping in the fused optimizer); no existing entry point changed, so the number
- *      stays. */
+ *      stays.
+ *      Later, still 3: fv_pack_weight_frags_batched, fv_mixer_conv_pool_bwd_dgrad_pk and
+ *      fv_mixer_combine_out_proj_addnorm_pk were ADDED (projection weights streamed in MFMA fragment order); the plain
+ *      entry points keep their signatures and the plain layout. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -422,6 +425,15 @@ int fv_mixer_combine_out_proj_addnorm(const void* xz, const void* skip, const fl
                                       const float* residual, const float* norm_weight, const float* row_scale,
                                       int rows_per_scale, void* y, float* residual_out, float* rstd, float eps,
                                       fv_stream_t stream);
+/* The same launch with W given as the FRAGMENT-MAJOR copy of out_proj.weight (fv_pack_weight_frags_batched, K = 384;
+ * ldw must be 384): every load of the weight stream reads 1 KiB contiguous.  Only load addresses differ: all outputs are
+ * bit-identical to fv_mixer_combine_out_proj_addnorm on the plain weight. */
+int fv_mixer_combine_out_proj_addnorm_pk(const void* xz, const void* skip, const float* yc, const float* ln_w,
+                                         const float* ln_b, float ln_eps, void* g, float* mean, float* rstd_ln, int batch,
+                                         int rows, int cols, int tok_stride_row, int tok_stride_col, const void* W,
+                                         long ldw, const float* residual, const float* norm_weight,
+                                         const float* row_scale, int rows_per_scale, void* y, float* residual_out,
+                                         float* rstd, float eps, fv_stream_t stream);
 
 /* fv_mixer_conv_pool_bwd2 + fv_gemm_bf16_dgrad_addnorm_bwd2 in ONE launch (round 6): the backward mirror of
  * fv_mixer_combine_out_proj_addnorm.  A workgroup owns four pooling rows of one image: it runs the conv + pool adjoint on
@@ -450,11 +462,30 @@ int fv_mixer_conv_pool_bwd_dgrad(const void* xz, const void* dskip, const float*
                                  const float* norm_weight, const float* row_scale, int rows_per_scale, void* dx,
                                  float* dresidual_in, float* partial_dw, const void* W2, void* C2, int N2, long ldw2,
                                  fv_stream_t stream);
+/* The same launch with W_in_t given as the FRAGMENT-MAJOR copy of in_proj.weight^T (fv_pack_weight_frags_batched,
+ * K = 768; ldwt must be 768).  Only load addresses differ: every output, the partial rows included, is bit-identical to
+ * fv_mixer_conv_pool_bwd_dgrad on the plain transposed weight.  W2 stays plain. */
+int fv_mixer_conv_pool_bwd_dgrad_pk(const void* xz, const void* dskip, const float* dxc, const void* dxc2,
+                                    const float* conv_w, const float* conv_b, const float* conv_w_b,
+                                    const float* conv_b_b, const float* D, const float* D_b, void* dxz,
+                                    float* conv_partials, int batch, int rows, int cols, int tok_stride_row,
+                                    int tok_stride_col, float scaling, const void* W_in_t, long ldwt,
+                                    const float* dresidual_out, const float* r, const float* rstd,
+                                    const float* norm_weight, const float* row_scale, int rows_per_scale, void* dx,
+                                    float* dresidual_in, float* partial_dw, const void* W2, void* C2, int N2, long ldw2,
+                                    fv_stream_t stream);
 
 /* dsts[j] (cols, rows) bf16 = srcs[j] (rows, cols)^T for up to 64 equal-shape matrices in one launch: the transposed
  * bf16 shadows of in_proj.weight that fv_mixer_conv_pool_bwd_dgrad reads (refreshed once per optimizer step). */
 int fv_transpose_bf16_batched(const void* const* srcs, void* const* dsts, int njobs, int rows, int cols,
                               fv_stream_t stream);
+
+/* Fragment-major copies of up to 64 weights in one launch.  srcs[j] is (192, K) bf16 with K contiguous, K = 384
+ * (out_proj.weight as stored) or 768 (in_proj.weight^T); dsts[j] holds the same 192 K elements in 16-byte units:
+ *   unit ((wv * K / 32 + ks) * 3 + nb) * 64 + lane  =  srcs[j][48 wv + 16 nb + (lane & 15)][32 ks + 8 (lane >> 4) .. + 8)
+ * (wv 0..3, ks 0..K/32-1, nb 0..2, lane 0..63) -- the MFMA operand lane `lane` of wave wv loads for column block nb at
+ * k step ks in the _pk launches above.  Both sides 16-byte aligned, no aliasing.  Refreshed once per optimizer step. */
+int fv_pack_weight_frags_batched(const void* const* srcs, void* const* dsts, int njobs, int K, fv_stream_t stream);
 
 /* fv_gemm_bf16_addnorm with a second GEMM phase: C2 (M, N2) bf16 = y @ W2^T, W2 (N2, N) bf16 row-major -- the block's
  * in_proj (mamba_simple_faster.py:189-193) computed from the normalised tile while it is still in LDS; bit-identical to
