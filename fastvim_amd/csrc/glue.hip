@@ -1,6 +1,7 @@
 // Small memory-bound ops around the backbone that the training step would otherwise run as strings of library
 // elementwise / reduce launches (each a 2.5-5 us node of the captured step):
 //   * patch unfold + cast: the k == stride patch-embed Conv2d (models/fastvim.py:95) as a GEMM operand;
+//   * batch-mode Mixup / CutMix of the images, on its own and folded into the patch unfold;
 //   * token mean pool and its adjoint (models/fastvim.py:529-531, final_pool_type == "mean");
 //   * the stochastic-depth keep table (timm DropPath: floor(keep + U) / keep, one row per DropPath module);
 //   * scale-by-a-device-scalar + cast (the loss gradient handed to the head), column sums (head bias gradient).
@@ -65,6 +66,118 @@ __global__ __launch_bounds__(256) void patch_unfold_kernel(const TI* __restrict_
   const int nv = gjn * Kp / EV;
   for (int e = threadIdx.x; e < nv; e += blockDim.x)
     reinterpret_cast<u32x4*>(dst)[e] = reinterpret_cast<const u32x4*>(tile)[e];
+}
+
+// ---- batch-mode Mixup / CutMix (timm.data.Mixup, mode='batch'): image b is mixed with image B-1-b --------------------
+// The parameters come from the mix-parameter block in device memory (fv_mix_params, include/fastvim_hip.h), never from a
+// launch argument: the host rewrites the block between replays of a captured launch.
+template <typename T> __device__ __forceinline__ float round_as(float v);      // v rounded to the storage type T
+template <> __device__ __forceinline__ float round_as<float>(float v) {
+  asm("" : "+v"(v));          // an opaque copy: the product that made it cannot be contracted into the sum that uses it
+  return v;
+}
+template <> __device__ __forceinline__ float round_as<bf16_t>(float v) { return bf16_bits_to_f32(f32_to_bf16_bits(v)); }
+
+enum { MIX_COPY = 0, MIX_MIXUP = 1, MIX_CUTMIX = 2 };
+__device__ __forceinline__ int mix_mode(const fv_mix_params& P) {
+  return P.use_cutmix ? MIX_CUTMIX : (P.lam == 1.f ? MIX_COPY : MIX_MIXUP);
+}
+
+// Pixels a (image b) and p (image B-1-b) at row y, columns x0 .. x0 + N - 1 -> the mixed pixels of both images.
+// Mixup is torch's x.mul(lam).add_(x.flip(0).mul_(1. - lam)) in the storage type T: each product rounded, then the sum
+// rounded (-ffast-math would contract one product into the add: 24 % of the pixels change).
+template <typename T, int N>
+__device__ __forceinline__ void mix_pixels(const fv_mix_params& P, int mode, int y, int x0, const float (&a)[N], const float (&p)[N],
+                                           float (&oa)[N], float (&op)[N]) {
+#pragma clang fp reassociate(off) contract(off)
+  if (mode == MIX_MIXUP) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      oa[k] = round_as<T>(round_as<T>(a[k] * P.lam) + round_as<T>(p[k] * P.one_minus_lam));
+      op[k] = round_as<T>(round_as<T>(p[k] * P.lam) + round_as<T>(a[k] * P.one_minus_lam));
+    }
+  } else {
+    const bool in_rows = mode == MIX_CUTMIX && y >= P.yl && y < P.yh;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      const bool in_box = in_rows && x0 + k >= P.xl && x0 + k < P.xh;
+      oa[k] = in_box ? p[k] : a[k];
+      op[k] = in_box ? a[k] : p[k];
+    }
+  }
+}
+
+// Stand-alone: a thread handles the same position of both images of a pair (two loads, two stores), so the batch is read
+// once and written once.  EV = 4: Vec4 accesses (W % 4 == 0 keeps a vector inside an image row); EV = 1: any shape.
+template <typename T, int EV>
+__global__ __launch_bounds__(256) void mix_batch_kernel(const T* __restrict__ x, T* __restrict__ out,
+                                                        const fv_mix_params* __restrict__ mp, int B, int n, int H, int W) {
+  const fv_mix_params P = *mp;
+  const int mode = mix_mode(P);
+  const size_t oa_ = (size_t)blockIdx.y * n, op_ = (size_t)(B - 1 - blockIdx.y) * n;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n / EV; e += gridDim.x * blockDim.x) {
+    const int i = e * EV, row = i / W;
+    float a[EV], p[EV], ra[EV], rp[EV];
+    if constexpr (EV == 4) {
+      Vec4<T>::ld(x + oa_ + i, a);
+      Vec4<T>::ld(x + op_ + i, p);
+    } else {
+      a[0] = io<T>::ld(x + oa_ + i);
+      p[0] = io<T>::ld(x + op_ + i);
+    }
+    mix_pixels<T, EV>(P, mode, row % H, i - row * W, a, p, ra, rp);
+    if constexpr (EV == 4) {
+      Vec4<T>::st(out + oa_ + i, ra);
+      Vec4<T>::st(out + op_ + i, rp);
+    } else {
+      io<T>::st(out + oa_ + i, ra[0]);
+      io<T>::st(out + op_ + i, rp[0]);
+    }
+  }
+}
+
+// patch_unfold_kernel over the two images of a pair at once: the same chunk of `gjc` patches of patch row gi of image
+// b = blockIdx.z and of image B-1-b.  Every input byte is read once, mixed in registers (in the image's type, as
+// mix_batch_kernel mixes it), converted once and placed in the image's own LDS tile; the two tiles leave as 16-byte stores.
+template <typename TI, typename TO>
+__global__ __launch_bounds__(1024) void patch_unfold_mix_kernel(const TI* __restrict__ img, TO* __restrict__ out,
+                                                               const fv_mix_params* __restrict__ mp, int B, int C, int H, int W,
+                                                               int ph, int pw, int gw, int gjc) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const fv_mix_params P = *mp;
+  const int mode = mix_mode(P);
+  const int gj0 = blockIdx.x * gjc, gi = blockIdx.y, ba = blockIdx.z, bp = B - 1 - ba;
+  const int gjn = min(gjc, gw - gj0);
+  const int Kp = C * ph * pw;                 // elements per patch row
+  const int xv = gjn * pw / 4;                // 4-element vectors per image-row segment of the chunk
+  TO* tile_a = reinterpret_cast<TO*>(smem);
+  TO* tile_p = tile_a + (size_t)gjc * Kp;
+  const size_t org = (size_t)gi * ph * W + (size_t)gj0 * pw;
+  const TI* src_a = img + (size_t)ba * C * H * W + org;
+  const TI* src_p = img + (size_t)bp * C * H * W + org;
+  for (int e = threadIdx.x; e < C * ph * xv; e += blockDim.x) {
+    const int row = e / xv, x = (e - row * xv) * 4;      // row = c * ph + pi
+    const int c = row / ph, pi = row - c * ph;
+    const size_t off = ((size_t)c * H + pi) * W + x;
+    float a[4], p[4], ra[4], rp[4];
+    Vec4<TI>::ld(src_a + off, a);
+    Vec4<TI>::ld(src_p + off, p);
+    mix_pixels<TI, 4>(P, mode, gi * ph + pi, gj0 * pw + x, a, p, ra, rp);
+    const int gj = x / pw, pj = x - gj * pw;
+    const size_t t = (size_t)gj * Kp + row * pw + pj;
+    Vec4<TO>::st(tile_a + t, ra);
+    Vec4<TO>::st(tile_p + t, rp);
+  }
+  __syncthreads();
+  const size_t chunk = ((size_t)gi * gw + gj0) * Kp, image = (size_t)gridDim.y * gw * Kp;
+  TO* dst_a = out + (size_t)ba * image + chunk;
+  TO* dst_p = out + (size_t)bp * image + chunk;
+  constexpr int EV = 16 / sizeof(TO);
+  const int nv = gjn * Kp / EV;
+  for (int e = threadIdx.x; e < nv; e += blockDim.x) {
+    reinterpret_cast<u32x4*>(dst_a)[e] = reinterpret_cast<const u32x4*>(tile_a)[e];
+    reinterpret_cast<u32x4*>(dst_p)[e] = reinterpret_cast<const u32x4*>(tile_p)[e];
+  }
 }
 
 // ---- token mean pool: out[b][d] = (1/L) sum_l x[b][l][d] ------------------------------------------------------------
@@ -237,6 +350,63 @@ extern "C" int fv_patch_unfold(const void* img, int img_dtype, void* out, int ou
   else if (out_dtype == FV_BF16) FV_UNF(bf16_t, bf16_t);
   else FV_UNF(bf16_t, float);
 #undef FV_UNF
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
+extern "C" int fv_mix_batch(const void* x, void* out, int dtype, int batch, int chans, int height, int width, const void* mix,
+                            fv_stream_t stream) {
+  FV_CHECK(x && out && mix && x != out, "mix_batch: null or aliased pointer (the op is out of place)");
+  FV_CHECK(dt_ok(dtype), "mix_batch: dtype must be fp32 or bf16");
+  FV_CHECK(batch > 0 && chans > 0 && height > 0 && width > 0, "mix_batch: empty dimension");
+  FV_CHECK(batch % 2 == 0, "mix_batch: batch mode pairs image b with image batch-1-b, the batch (%d) must be even", batch);
+  const long n = (long)chans * height * width;
+  FV_CHECK(n < (1l << 31) && batch / 2 <= 65535, "mix_batch: image or batch too large");
+  const size_t esz = dtype == FV_F32 ? 4 : 2;
+  const bool vec = width % 4 == 0 && ((uintptr_t)x % (4 * esz)) == 0 && ((uintptr_t)out % (4 * esz)) == 0;
+  const long work = vec ? n / 4 : n;
+  const dim3 grid(fv_cdiv(work, 256) < 1024 ? fv_cdiv(work, 256) : 1024, batch / 2), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const fv_mix_params* mp = (const fv_mix_params*)mix;
+#define FV_MIXB(T, EV) hipLaunchKernelGGL((mix_batch_kernel<T, EV>), grid, block, 0, st, (const T*)x, (T*)out, mp, batch, (int)n, height, width)
+  if (dtype == FV_F32) { if (vec) FV_MIXB(float, 4); else FV_MIXB(float, 1); }
+  else { if (vec) FV_MIXB(bf16_t, 4); else FV_MIXB(bf16_t, 1); }
+#undef FV_MIXB
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
+extern "C" int fv_patch_unfold_mix(const void* img, int img_dtype, void* out, int out_dtype, int batch, int chans, int height,
+                                   int width, int ph, int pw, const void* mix, fv_stream_t stream) {
+  FV_CHECK(img && out && mix, "patch_unfold_mix: null pointer");
+  FV_CHECK(dt_ok(img_dtype) && dt_ok(out_dtype), "patch_unfold_mix: dtypes must be fp32 or bf16");
+  FV_CHECK(batch > 0 && chans > 0 && ph > 0 && pw > 0 && height >= ph && width >= pw, "patch_unfold_mix: empty dimension");
+  FV_CHECK(batch % 2 == 0, "patch_unfold_mix: batch mode pairs image b with image batch-1-b, the batch (%d) must be even", batch);
+  FV_CHECK(height % ph == 0 && width % pw == 0, "patch_unfold_mix: image %dx%d is not whole %dx%d patches", height, width, ph, pw);
+  FV_CHECK(pw % 8 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)out & 15) == 0,
+           "patch_unfold_mix: patch width must be a multiple of 8 and the buffers 16-byte aligned");
+  const int gh = height / ph, gw = width / pw;
+  const size_t osz = out_dtype == FV_F32 ? 4 : 2;
+  // Two tiles per workgroup.  What this kernel is short of is loads in flight per byte of LDS: with fv_patch_unfold's
+  // shape (16 patches, 256 threads) the doubled tile halves the workgroups a CU holds, and the launch ran 12 % behind
+  // the plain unfold; 8 patches per tile -- the plain kernel's LDS footprint -- under 512 threads runs ahead of it
+  // (*Mixup*).  fv_patch_unfold's own limit (16 patches in 64 KB) is then the limit here too.
+  const size_t per_patch = 2 * (size_t)chans * ph * pw * osz;
+  const int gjc = fv_tune("FASTVIM_UNFOLD_MIX_GJ", UNF_GJ / 2);
+  const int threads = fv_tune("FASTVIM_UNFOLD_MIX_THREADS", 512);
+  const size_t smem = gjc * per_patch;
+  FV_CHECK(gjc > 0 && smem <= 64 * 1024, "patch_unfold_mix: %d x %d x %d patches do not fit the staging tiles", chans, ph, pw);
+  FV_CHECK(threads >= 64 && threads <= 1024 && threads % 64 == 0, "patch_unfold_mix: bad workgroup size %d", threads);
+  FV_CHECK(gh <= 65535 && batch / 2 <= 65535, "patch_unfold_mix: grid too large");
+  const dim3 grid(fv_cdiv(gw, gjc), gh, batch / 2), block(threads);
+  hipStream_t st = (hipStream_t)stream;
+  const fv_mix_params* mp = (const fv_mix_params*)mix;
+#define FV_UNFM(TI, TO) hipLaunchKernelGGL((patch_unfold_mix_kernel<TI, TO>), grid, block, smem, st, (const TI*)img, (TO*)out, mp, batch, chans, height, width, ph, pw, gw, gjc)
+  if (img_dtype == FV_F32 && out_dtype == FV_BF16) FV_UNFM(float, bf16_t);
+  else if (img_dtype == FV_F32) FV_UNFM(float, float);
+  else if (out_dtype == FV_BF16) FV_UNFM(bf16_t, bf16_t);
+  else FV_UNFM(bf16_t, float);
+#undef FV_UNFM
   FV_LAUNCH_CHECK();
   return FV_OK;
 }

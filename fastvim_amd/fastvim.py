@@ -206,9 +206,11 @@ class PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size)
         self.norm = norm_layer(embed_dim) if norm_layer else nn.Identity()
 
-    def forward(self, x, pos_embed=None):
+    def forward(self, x, pos_embed=None, mix=None):
         """``pos_embed`` (1, L, D), optional: added in the same epilogue as the conv bias (only for the
-        row-major, flattened token order)."""
+        row-major, flattened token order).  ``mix`` (a ``fastvim_amd.mixup.Mixup``), optional: the batch is embedded as
+        mixed by the parameters its device block holds -- inside the unfold kernel where that one applies (the mixed
+        images are never written), else by one ``fv_mix_batch`` launch in front."""
         B, C, H, W = x.shape
         if self.strict_img_size:
             assert H == self.img_size[0], f"Input height ({H}) doesn't match model ({self.img_size[0]})."
@@ -216,6 +218,13 @@ class PatchEmbed(nn.Module):
         elif not self.dynamic_img_pad:
             assert H % self.patch_size[0] == 0, f"Input height ({H}) should be divisible by patch size ({self.patch_size[0]})."
             assert W % self.patch_size[1] == 0, f"Input width ({W}) should be divisible by patch size ({self.patch_size[1]})."
+        if mix is not None:
+            mix._check_batch(x)
+            if x.requires_grad and torch.is_grad_enabled():
+                raise RuntimeError("PatchEmbed: mix= has no gradient with respect to the images")
+            padded = self.dynamic_img_pad and (H % self.patch_size[0] or W % self.patch_size[1])
+            if padded or not (G.patch_unfold_ok(x, *self.patch_size) and _compute_dtype(x) in (torch.float32, torch.bfloat16)):
+                x, mix = mix.mix_batch(x), None      # the unfold kernel does not apply: mix first, one launch, then as ever
         if self.dynamic_img_pad:
             pad_h = (self.patch_size[0] - H % self.patch_size[0]) % self.patch_size[0]
             pad_w = (self.patch_size[1] - W % self.patch_size[1]) % self.patch_size[1]
@@ -232,7 +241,10 @@ class PatchEmbed(nn.Module):
         # (the kernel has no autograd node: an image that requires grad takes the strided copy below, whose adjoint --
         # the fold -- autograd knows)
         want_dx = x.requires_grad and torch.is_grad_enabled()
-        if G.patch_unfold_ok(x, ph, pw) and cdt in (torch.float32, torch.bfloat16) and not want_dx:
+        unfold_ok = G.patch_unfold_ok(x, ph, pw) and cdt in (torch.float32, torch.bfloat16) and not want_dx
+        if unfold_ok and mix is not None:
+            patches = G.patch_unfold_mix(x, ph, pw, cdt, mix.block(x.device))      # the same launch, over pairs of images
+        elif unfold_ok:
             patches = G.patch_unfold(x, ph, pw, cdt)                # one HIP launch through LDS: 16-byte accesses both ways
         else:
             patches = torch.empty(B, gh * gw, C * ph * pw, device=x.device, dtype=cdt)
@@ -409,8 +421,12 @@ class VisionMamba(nn.Module):
 
     # forward_features (models/fastvim.py:484-546) in three pieces, so that a training step can be cut into segments of
     # layers (fastvim_amd/pipeline.py: gradient buckets exchanged while the next segment's backward runs)
-    def _embed(self, x):
+    def _embed(self, x, mix=None):
+        """``mix``: a ``fastvim_amd.mixup.Mixup`` whose current parameters mix the batch on its way into the patch
+        embedding (training only: ``eval()`` paths never mix)."""
         B, _, H, W = x.shape
+        if not self.training:
+            mix = None
         if self.if_abs_pos_embed:
             H, W = math.ceil(H / self.patch_size), math.ceil(W / self.patch_size)
             hw = (H, W) if self.patch_embed.scanpath_type == "rowwise" else (W, H)
@@ -419,11 +435,11 @@ class VisionMamba(nn.Module):
                 # the model with the target img_size instead
                 raise RuntimeError(f"input grid {H}x{W} differs from the model's {self.token_size}; "
                                    "build VisionMamba with the matching img_size")
-            x = self.patch_embed(x, pos_embed=self.pos_embed)     # x + pos_embed (:500) in the epilogue
+            x = self.patch_embed(x, pos_embed=self.pos_embed, mix=mix)     # x + pos_embed (:500) in the epilogue
             x = self.pos_drop(x)
         else:
             H, W = math.ceil(H / self.patch_size), math.ceil(W / self.patch_size)
-            x = self.patch_embed(x)
+            x = self.patch_embed(x, mix=mix)
         if self.training:
             DropPath.predraw([l.drop_path for l in self.layers] + [self.drop_path], x.shape[0], x.device)
         return x, (H, W)

@@ -26,6 +26,37 @@ def patch_unfold_ok(x, ph, pw):
             and x.shape[2] % ph == 0 and x.shape[3] % pw == 0 and x.shape[1] * ph * pw * 16 * 4 <= 64 * 1024)
 
 
+def mix_batch(x, block, out=None):
+    """Batch-mode Mixup / CutMix of (B, C, H, W) images, out of place: ``out[b] = mix(x[b], x[B-1-b])`` with the
+    parameters the device ``block`` (fastvim_amd.mixup.Mixup.block) holds at the time the kernel runs.  One launch that
+    reads the batch once and writes it once (timm: flip, mul_, mul_, add_)."""
+    L.require_gpu(x, block)
+    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"mix_batch: expected (B, C, H, W) fp32 or bf16 images, got {tuple(x.shape)} {x.dtype}")
+    B, C, H, W = x.shape
+    x = x.contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous():
+        raise RuntimeError("mix_batch: `out` must be a contiguous tensor of the input's shape and dtype")
+    rc = L.lib().fv_mix_batch(L.ptr(x), L.ptr(out), L.i32(L.dtype_code(x.dtype)), L.i32(B), L.i32(C), L.i32(H), L.i32(W),
+                              L.ptr(block), L.stream_of(x))
+    L.check(rc, "mix_batch")
+    return out
+
+
+def patch_unfold_mix(x, ph, pw, out_dtype, block):
+    """``patch_unfold`` of the mixed batch in one launch (the mixed images never exist in memory): bit for bit
+    ``patch_unfold(mix_batch(x, block), ph, pw, out_dtype)``.  Applicable where ``patch_unfold_ok`` and the batch is even."""
+    B, C, H, W = x.shape
+    x = x.contiguous()
+    out = torch.empty(B, (H // ph) * (W // pw), C * ph * pw, device=x.device, dtype=out_dtype)
+    rc = L.lib().fv_patch_unfold_mix(L.ptr(x), L.i32(L.dtype_code(x.dtype)), L.ptr(out), L.i32(L.dtype_code(out_dtype)),
+                                     L.i32(B), L.i32(C), L.i32(H), L.i32(W), L.i32(ph), L.i32(pw), L.ptr(block), L.stream_of(x))
+    L.check(rc, "patch_unfold_mix")
+    return out
+
+
 def gemm_rowbias(a, w, table):
     """fp32 (M, N) = bf16_round(a (M, K) @ w (N, K)^T) + table[m mod period]: bf16 operands, table (period, N) fp32."""
     M, K = a.shape

@@ -17,6 +17,7 @@ exchanged and the chain computes what the single-graph step computes: bit for bi
 the shipped default (``gemm.fill_splits`` re-cuts a segment's smaller weight-gradient groups into more K slices) the
 same sums are taken in another order and the two agree to rounding (tests/test_pipeline_gpu.py asserts both).
 """
+import inspect
 import warnings
 
 import torch
@@ -28,15 +29,29 @@ class SegmentedTrainStep:
     ``loss_fn(logits, target) -> scalar``.  ``x`` / ``target`` are the static input buffers the graphs read; copy
     new batches into them between steps.
 
+    ``mixup`` (a ``fastvim_amd.mixup.Mixup``, with ``loss_fn = mixup.criterion()`` and ``target`` the (B,) int64 labels):
+    the batch is mixed inside the step with the parameters of the last ``mixup.sample()``, which the caller issues between
+    steps like ``opt.set_lr``:  ``x.copy_(batch); labels.copy_(y); mixup.sample(); opt.set_lr(lr); step.step()``.
+
     Capture needs ``warmup`` eager steps first (allocator, lazily built buffers, RCCL communicators).  They are real
     steps on whatever ``x`` / ``target`` hold, so the training state they touch -- parameters, bf16 shadow, Adam moments,
     EMA, step count, the CPU and GPU RNG streams -- is snapshotted before and put back after them: constructing the
     step object leaves the model, the optimizer and the DropPath stream exactly as it found them."""
 
     def __init__(self, model, flat, opt, loss_fn, x, target, n_segments=3, amp_dtype=torch.bfloat16, use_graph=True,
-                 warmup=2):
+                 warmup=2, mixup=None):
         self.model, self.flat, self.opt, self.loss_fn = model, flat, opt, loss_fn
         self.x, self.target, self.amp_dtype = x, target, amp_dtype
+        # batch-mode Mixup / CutMix inside the step: the images are mixed on their way into the patch embedding by whatever
+        # the Mixup's device block holds when the graph RUNS -- the caller calls mixup.sample() between steps, the step never
+        # does -- and `target` is the (B,) int64 label buffer that mixup.criterion() turns into the soft target
+        self.mixup, self._embed_takes_mix, self._x_mixed = mixup, False, None
+        if mixup is not None:
+            mixup._check_batch(x)
+            mixup.bind(x)                                # image size for the boxes; the block exists before any capture
+            self._embed_takes_mix = "mix" in inspect.signature(model._embed).parameters
+            if not self._embed_takes_mix:                # such a model gets the mixed batch from one fv_mix_batch launch
+                self._x_mixed = torch.empty_like(x, memory_format=torch.contiguous_format)
         self.exchange = flat.make_exchange(n_segments)
         self.runs = self.exchange.layers                 # (lo, hi) block ranges in BACKWARD order
         self.K = len(self.runs)
@@ -56,7 +71,12 @@ class SegmentedTrainStep:
         self.flat.zero_grad()
         cuts = []              # per run in FORWARD order: (inputs (leaves) or None, outputs)
         with torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.amp_dtype != torch.float32):
-            h, _ = m._embed(self.x)
+            if self.mixup is None:
+                h, _ = m._embed(self.x)
+            elif self._embed_takes_mix:
+                h, _ = m._embed(self.x, mix=self.mixup)
+            else:
+                h, _ = m._embed(self.mixup.mix_batch(self.x, out=self._x_mixed))
             res, pend = None, None
             fwd_runs = self.runs[::-1]
             open_runs = hasattr(m, "_run_layers_open")

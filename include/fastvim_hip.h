@@ -46,7 +46,9 @@ const char* fv_last_error(void);
  *      stays.
  *      Later, still 3: fv_pack_weight_frags_batched, fv_mixer_conv_pool_bwd_dgrad_pk and
  *      fv_mixer_combine_out_proj_addnorm_pk were ADDED (projection weights streamed in MFMA fragment order); the plain
- *      entry points keep their signatures and the plain layout. */
+ *      entry points keep their signatures and the plain layout.
+ *      Later, still 3: fv_mix_batch, fv_patch_unfold_mix, fv_mixup_target and fv_label_ce were ADDED (batch Mixup /
+ *      CutMix and the losses on integer labels). */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -583,6 +585,60 @@ int fv_droppath_table(float* table, const float* keep, const float* inv_keep, in
 int fv_scale_cast(const float* x, const float* scale, void* y, int y_dtype, size_t n, fv_stream_t stream);
 /* out[c] (+)= sum_r x[r][c], x (rows, cols) fp32 or bf16, fixed order: a bias gradient. */
 int fv_column_sum(const void* x, int dtype, float* out, int rows, int cols, int accumulate, fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Batch-mode Mixup / CutMix (timm.data.Mixup, mode='batch'; the first line of the reference's training_step,
+ * imagenet_classification/supervised_imagenet.py:116-139) and the losses on integer labels (:80-92).
+ *
+ * Image b is mixed with image batch-1-b.  Everything below reads the augmentation's parameters from a MIX-PARAMETER
+ * BLOCK in device memory -- 32 bytes, 16-byte aligned, laid out as `struct fv_mix_params` -- and takes none of them
+ * as a launch argument: the host rewrites the block between two replays of a captured launch, and the replay mixes
+ * with the new values.
+ *   lam            fp32 weight of the image itself / of labels[b]
+ *   one_minus_lam  fp32 rounding of the DOUBLE 1 - lam (what Python's `1. - lam` hands to torch), weight of the partner
+ *   use_cutmix     0: mixup, out = fl(x * lam) + fl(x_partner * one_minus_lam), the two products rounded separately
+ *                     to the storage type, then added (no fused multiply-add: that is torch's x.mul(lam).add_(
+ *                     x.flip(0).mul_(1. - lam)) bit for bit); lam == 1 is a plain copy
+ *                  1: cutmix, pixels with yl <= y < yh and xl <= x < xh come from the partner image, all others
+ *                     from the image itself (an empty box is a plain copy); lam only weighs the labels
+ *   yl, yh, xl, xh the box, in pixels
+ * ---------------------------------------------------------------------- */
+typedef struct fv_mix_params {
+  float lam;
+  float one_minus_lam;
+  int32_t use_cutmix;
+  int32_t yl, yh, xl, xh;
+  int32_t reserved;
+} fv_mix_params;
+
+/* out[b] = mix(x[b], x[batch-1-b]), out of place; x, out (batch, chans, height, width) of one dtype (fp32 or bf16),
+ * batch even.  One thread handles the same position of both images of a pair: the batch is read once and written
+ * once. */
+int fv_mix_batch(const void* x, void* out, int dtype, int batch, int chans, int height, int width, const void* mix,
+                 fv_stream_t stream);
+/* fv_patch_unfold of the mixed batch in one launch: the mixed image never exists in memory.  A workgroup unfolds the
+ * same chunk of a patch row of both images of a pair; a pixel is mixed in the image's dtype exactly as fv_mix_batch
+ * mixes it and rounded to out_dtype once, so out equals fv_patch_unfold(fv_mix_batch(img)) bit for bit.  Arguments
+ * and limits of fv_patch_unfold; batch even. */
+int fv_patch_unfold_mix(const void* img, int img_dtype, void* out, int out_dtype, int batch, int chans, int height,
+                        int width, int ph, int pw, const void* mix, fv_stream_t stream);
+/* The dense soft target timm.data.Mixup returns: target (batch, classes) fp32 =
+ *   fl(y1 * lam) + fl(y2 * one_minus_lam),  y1 = one_hot(labels), y2 = one_hot(labels reversed along the batch),
+ * one_hot with off = smoothing / classes elsewhere and on = 1 - smoothing + off at the label (both computed in double,
+ * rounded to fp32).  labels (batch,) int64; a label outside [0, classes) marks no class. */
+int fv_mixup_target(const int64_t* labels, float* target, int batch, int classes, double smoothing, const void* mix,
+                    fv_stream_t stream);
+/* fv_soft_target_ce on the target fv_mixup_target would write, built in registers from labels[b], labels[batch-1-b]
+ * and the block: same row body, bit-identical loss_rows / loss / dlogits, no (batch, classes) target tensor.
+ *   mix == NULL    no partner: the target is one_hot(labels) itself -- torch.nn.CrossEntropyLoss (mean reduction) with
+ *                  smoothing == 0, timm.loss.LabelSmoothingCrossEntropy with smoothing > 0; batch may be odd
+ *   dlogits        NULL: value only (validation)
+ *   correct_rows, n_correct   NULL, or (batch,) / 1 int32: correct_rows[b] = (argmax_c logits[b][c] == labels[b]), the
+ *                  first maximum on a tie, and their sum (fixed order) -- the validation step's top-1 count
+ * classes <= 2048. */
+int fv_label_ce(const void* logits, int logits_dtype, const int64_t* labels, const void* mix, double smoothing,
+                float* loss_rows, float* loss, float* dlogits, int32_t* correct_rows, int32_t* n_correct, int batch,
+                int classes, fv_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Fused AdamW (decoupled weight decay, bias correction; torch.optim.AdamW semantics) over a flat fp32
