@@ -2,6 +2,8 @@
 // elementwise / reduce launches (each a 2.5-5 us node of the captured step):
 //   * patch unfold + cast: the k == stride patch-embed Conv2d (models/fastvim.py:95) as a GEMM operand;
 //   * batch-mode Mixup / CutMix of the images, on its own and folded into the patch unfold;
+//   * the channel models' embed under hierarchical channel sampling: per-channel patch unfold with the channel gather, the
+//     per-token table of the patch GEMM's epilogue, the scatter of the channel-embedding gradient rows;
 //   * token mean pool and its adjoint (models/fastvim.py:529-531, final_pool_type == "mean");
 //   * the stochastic-depth keep table (timm DropPath: floor(keep + U) / keep, one row per DropPath module);
 //   * scale-by-a-device-scalar + cast (the loss gradient handed to the head), column sums (head bias gradient).
@@ -66,6 +68,81 @@ __global__ __launch_bounds__(256) void patch_unfold_kernel(const TI* __restrict_
   const int nv = gjn * Kp / EV;
   for (int e = threadIdx.x; e < nv; e += blockDim.x)
     reinterpret_cast<u32x4*>(dst)[e] = reinterpret_cast<const u32x4*>(tile)[e];
+}
+
+// ---- per-channel patch unfold with a channel gather (hierarchical channel sampling of the channel models) --------------
+//   out[b][(p*n + k)][pi*pw + pj] = img[b][sel[k]][gi*ph + pi][gj*pw + pj],  p = gi*gw + gj  (COLWISE: gj*gh + gi)
+// patch_unfold_kernel with the channel looked up in `sel` (device memory, read when the kernel runs; NULL: identity) and
+// `gjc` patches per workgroup chosen by the host (n * ph * pw elements per patch must fit the tile).  Rowwise the gjc
+// patches are one contiguous stretch of `out`; colwise each patch's n*ph*pw elements are one.  An index outside
+// [0, Ctot) is clamped: a block that was never written must not make the kernel read outside the image.
+__device__ __forceinline__ int sel_channel(const int32_t* __restrict__ sel, int k, int Ctot) {
+  return sel ? min(max(sel[k], 0), Ctot - 1) : k;
+}
+
+template <typename TI, typename TO, bool COLWISE>
+__global__ __launch_bounds__(256) void patch_unfold_chan_kernel(const TI* __restrict__ img, TO* __restrict__ out,
+                                                                const int32_t* __restrict__ sel, int n, int Ctot, int H, int W,
+                                                                int ph, int pw, int gw, int gjc) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  TO* tile = reinterpret_cast<TO*>(smem);
+  const int gj0 = blockIdx.x * gjc, gi = blockIdx.y, b = blockIdx.z, gh = gridDim.y;
+  const int gjn = min(gjc, gw - gj0);
+  const int Kp = n * ph * pw;                 // elements per patch position
+  const int xv = gjn * pw / 4;                // 4-element vectors per image-row segment of the chunk
+  const TI* src = img + ((size_t)b * Ctot * H + (size_t)gi * ph) * W + (size_t)gj0 * pw;
+  for (int e = threadIdx.x; e < n * ph * xv; e += blockDim.x) {
+    const int row = e / xv, x = (e - row * xv) * 4;      // row = k * ph + pi
+    const int k = row / ph, pi = row - k * ph;
+    float v[4];
+    Vec4<TI>::ld(src + ((size_t)sel_channel(sel, k, Ctot) * H + pi) * W + x, v);
+    const int gj = x / pw, pj = x - gj * pw;
+    Vec4<TO>::st(tile + (size_t)gj * Kp + row * pw + pj, v);
+  }
+  __syncthreads();
+  constexpr int EV = 16 / sizeof(TO);
+  if constexpr (!COLWISE) {
+    TO* dst = out + (((size_t)b * gh + gi) * gw + gj0) * Kp;
+    const int nv = gjn * Kp / EV;
+    for (int e = threadIdx.x; e < nv; e += blockDim.x)
+      reinterpret_cast<u32x4*>(dst)[e] = reinterpret_cast<const u32x4*>(tile)[e];
+  } else {
+    const int pv = Kp / EV;                   // 16-byte vectors per patch position (pw % 8 == 0)
+    for (int e = threadIdx.x; e < gjn * pv; e += blockDim.x) {
+      const int gj = e / pv, r = e - gj * pv;
+      TO* dst = out + (((size_t)b * gw + gj0 + gj) * gh + gi) * Kp;
+      reinterpret_cast<u32x4*>(dst)[r] = reinterpret_cast<const u32x4*>(tile)[e];
+    }
+  }
+}
+
+// table[(p*n + k)][d] = (chan[sel[k]][d] + bias[d]) + pos[p][d] in fp32, the sums in this association (what the eager
+// epilogue of PatchEmbedPerChannel computes term by term); bias / pos may be absent.
+__global__ __launch_bounds__(256) void chan_embed_table_kernel(const float* __restrict__ chan, const float* __restrict__ bias,
+                                                               const float* __restrict__ pos, float* __restrict__ table,
+                                                               const int32_t* __restrict__ sel, int n, int Ctot, int D, size_t total) {
+#pragma clang fp reassociate(off) contract(off)
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int d = (int)(i % D);
+    const size_t t = i / D;                   // token = p * n + k
+    const int k = (int)(t % n);
+    const size_t p = t / n;
+    float v = chan[(size_t)sel_channel(sel, k, Ctot) * D + d];
+    if (bias) v = v + bias[d];
+    if (pos) v = v + pos[p * D + d];
+    table[i] = v;
+  }
+}
+
+// d_table[sel[k]][d] += d_chan[k][d]: the indices of a subset are distinct, so an element of d_table has one owner.
+__global__ __launch_bounds__(256) void chan_embed_scatter_kernel(const float* __restrict__ d_chan, float* __restrict__ d_table,
+                                                                 const int32_t* __restrict__ sel, int n, int Ctot, int D) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * D) return;
+  const int k = i / D, d = i - k * D;
+  const int c = sel ? sel[k] : k;
+  if (c < 0 || c >= Ctot) return;
+  d_table[(size_t)c * D + d] += d_chan[i];
 }
 
 // ---- batch-mode Mixup / CutMix (timm.data.Mixup, mode='batch'): image b is mixed with image B-1-b --------------------
@@ -350,6 +427,65 @@ extern "C" int fv_patch_unfold(const void* img, int img_dtype, void* out, int ou
   else if (out_dtype == FV_BF16) FV_UNF(bf16_t, bf16_t);
   else FV_UNF(bf16_t, float);
 #undef FV_UNF
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
+extern "C" int fv_patch_unfold_chan(const void* img, int img_dtype, void* out, int out_dtype, int batch, int chans_total,
+                                    int height, int width, int ph, int pw, const int32_t* sel, int n_sel, int colwise,
+                                    fv_stream_t stream) {
+  FV_CHECK(img && out, "patch_unfold_chan: null pointer");
+  FV_CHECK(dt_ok(img_dtype) && dt_ok(out_dtype), "patch_unfold_chan: dtypes must be fp32 or bf16");
+  FV_CHECK(batch > 0 && chans_total > 0 && ph > 0 && pw > 0 && height >= ph && width >= pw, "patch_unfold_chan: empty dimension");
+  FV_CHECK(n_sel > 0 && n_sel <= chans_total, "patch_unfold_chan: %d selected channels of %d", n_sel, chans_total);
+  FV_CHECK(height % ph == 0 && width % pw == 0, "patch_unfold_chan: image %dx%d is not whole %dx%d patches", height, width, ph, pw);
+  FV_CHECK(pw % 8 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)out & 15) == 0,
+           "patch_unfold_chan: patch width must be a multiple of 8 and the buffers 16-byte aligned");
+  const int gh = height / ph, gw = width / pw;
+  const size_t osz = out_dtype == FV_F32 ? 4 : 2;
+  // patches per workgroup: at most UNF_GJ, a tile of at most 32 KB (two workgroups per CU keep loads in flight while
+  // one drains its tile), and the patch row cut into equal chunks (14 patches under a limit of 8: 7 + 7, not 8 + 6)
+  const size_t per_patch = (size_t)n_sel * ph * pw * osz;
+  FV_CHECK(per_patch <= 64 * 1024, "patch_unfold_chan: %d x %d x %d patches do not fit the staging tile", n_sel, ph, pw);
+  int fit = (int)((32 * 1024) / per_patch);
+  fit = fit < 1 ? 1 : (fit > UNF_GJ ? UNF_GJ : fit);
+  const int gjc = fv_cdiv(gw, fv_cdiv(gw, fit));
+  const size_t smem = gjc * per_patch;
+  FV_CHECK(gh <= 65535 && batch <= 65535, "patch_unfold_chan: grid too large");
+  const dim3 grid(fv_cdiv(gw, gjc), gh, batch), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define FV_UNFC2(TI, TO, CW) hipLaunchKernelGGL((patch_unfold_chan_kernel<TI, TO, CW>), grid, block, smem, st, (const TI*)img, (TO*)out, sel, n_sel, chans_total, height, width, ph, pw, gw, gjc)
+#define FV_UNFC(TI, TO) do { if (colwise) FV_UNFC2(TI, TO, true); else FV_UNFC2(TI, TO, false); } while (0)
+  if (img_dtype == FV_F32 && out_dtype == FV_BF16) FV_UNFC(float, bf16_t);
+  else if (img_dtype == FV_F32) FV_UNFC(float, float);
+  else if (out_dtype == FV_BF16) FV_UNFC(bf16_t, bf16_t);
+  else FV_UNFC(bf16_t, float);
+#undef FV_UNFC
+#undef FV_UNFC2
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
+extern "C" int fv_chan_embed_table(const float* chan_table, const float* bias, const float* pos, float* table, const int32_t* sel,
+                                   int n_sel, int chans_total, int positions, int dim, fv_stream_t stream) {
+  FV_CHECK(chan_table && table, "chan_embed_table: null pointer");
+  FV_CHECK(n_sel > 0 && n_sel <= chans_total && positions > 0 && dim > 0, "chan_embed_table: bad shape (%d of %d channels, %d positions, dim %d)",
+           n_sel, chans_total, positions, dim);
+  const size_t total = (size_t)positions * n_sel * dim;
+  const long blocks = fv_cdiv((long)total, 256l);
+  hipLaunchKernelGGL(chan_embed_table_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
+                     chan_table, bias, pos, table, sel, n_sel, chans_total, dim, total);
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
+extern "C" int fv_chan_embed_scatter(const float* d_chan, float* d_table, const int32_t* sel, int n_sel, int chans_total, int dim,
+                                     fv_stream_t stream) {
+  FV_CHECK(d_chan && d_table, "chan_embed_scatter: null pointer");
+  FV_CHECK(n_sel > 0 && n_sel <= chans_total && dim > 0 && (long)n_sel * dim < (1l << 31), "chan_embed_scatter: bad shape (%d of %d channels, dim %d)",
+           n_sel, chans_total, dim);
+  hipLaunchKernelGGL(chan_embed_scatter_kernel, dim3(fv_cdiv(n_sel * dim, 256)), dim3(256), 0, (hipStream_t)stream,
+                     d_chan, d_table, sel, n_sel, chans_total, dim);
   FV_LAUNCH_CHECK();
   return FV_OK;
 }

@@ -26,6 +26,47 @@ def patch_unfold_ok(x, ph, pw):
             and x.shape[2] % ph == 0 and x.shape[3] % pw == 0 and x.shape[1] * ph * pw * 16 * 4 <= 64 * 1024)
 
 
+def patch_unfold_chan_ok(x, ph, pw, n_sel):
+    return (x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and pw % 8 == 0
+            and x.shape[2] % ph == 0 and x.shape[3] % pw == 0 and n_sel * ph * pw * 4 <= 64 * 1024)
+
+
+def patch_unfold_chan(x, ph, pw, out_dtype, sel, n_sel, colwise=False):
+    """(B, Ctot, H, W) -> (B, P * n_sel, ph*pw) in ``out_dtype``, tokens in (row, col, channel) order (``colwise``: (col, row,
+    channel)), channel k of the output = ``x[:, sel[k]]``: the per-channel patches of the shared projection, gathered,
+    unfolded and cast in one pass.  ``sel``: int32 device tensor read when the kernel runs, or None (the first ``n_sel``
+    channels)."""
+    B, Ctot, H, W = x.shape
+    x = x.contiguous()
+    out = torch.empty(B, (H // ph) * (W // pw) * n_sel, ph * pw, device=x.device, dtype=out_dtype)
+    rc = L.lib().fv_patch_unfold_chan(L.ptr(x), L.i32(L.dtype_code(x.dtype)), L.ptr(out), L.i32(L.dtype_code(out_dtype)),
+                                      L.i32(B), L.i32(Ctot), L.i32(H), L.i32(W), L.i32(ph), L.i32(pw), L.ptr(sel), L.i32(n_sel),
+                                      L.i32(bool(colwise)), L.stream_of(x))
+    L.check(rc, "patch_unfold_chan")
+    return out
+
+
+def chan_embed_table(chan_table, bias, pos, sel, n_sel, positions):
+    """fp32 (positions * n_sel, D): ``table[p * n_sel + k] = (chan_table[sel[k]] + bias) + pos[p]`` -- the per-token table
+    the channel models' patch GEMM adds in its epilogue.  ``chan_table`` (Ctot, D), ``bias`` (D) or None, ``pos``
+    (positions, D) or None, all fp32 and contiguous."""
+    Ctot, D = chan_table.shape
+    table = torch.empty(positions * n_sel, D, device=chan_table.device, dtype=torch.float32)
+    rc = L.lib().fv_chan_embed_table(L.ptr(chan_table), L.ptr(bias), L.ptr(pos), L.ptr(table), L.ptr(sel), L.i32(n_sel),
+                                     L.i32(Ctot), L.i32(positions), L.i32(D), L.stream_of(chan_table))
+    L.check(rc, "chan_embed_table")
+    return table
+
+
+def chan_embed_scatter_(d_table, d_chan, sel):
+    """In place: ``d_table[sel[k]] += d_chan[k]`` (fp32; ``sel`` None: k); the other rows are not touched."""
+    n_sel, D = d_chan.shape
+    rc = L.lib().fv_chan_embed_scatter(L.ptr(d_chan), L.ptr(d_table), L.ptr(sel), L.i32(n_sel), L.i32(d_table.shape[0]), L.i32(D),
+                                       L.stream_of(d_chan))
+    L.check(rc, "chan_embed_scatter")
+    return d_table
+
+
 def mix_batch(x, block, out=None):
     """Batch-mode Mixup / CutMix of (B, C, H, W) images, out of place: ``out[b] = mix(x[b], x[B-1-b])`` with the
     parameters the device ``block`` (fastvim_amd.mixup.Mixup.block) holds at the time the kernel runs.  One launch that

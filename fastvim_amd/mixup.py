@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from ._devblock import BlockWriter
 
 MixParams = collections.namedtuple("MixParams", "lam use_cutmix box")      # box = (yl, yh, xl, xh) in pixels
 
@@ -58,7 +59,7 @@ class Mixup:
         self._hw = None                      # image size the CutMix box is drawn for
         self._params = MixParams(1.0, False, (0, 0, 0, 0))
         self._block = None                   # the device block, made on first need
-        self._host, self._turn = None, 0     # pinned staging copies of it, used in turn: [tensor, event of its last copy]
+        self._writer = None                  # its BlockWriter (pinned staging ring), made with it
 
     # ------------------------------------------------------------------ host side
     def bind(self, x):
@@ -143,7 +144,7 @@ class Mixup:
             if device.type != "cuda":
                 raise RuntimeError("fastvim_amd ops run on the GPU only (HIP kernels); the mix-parameter block needs a GPU device")
             self._block = torch.zeros(8, device=device, dtype=torch.int32)
-            self._host = [[torch.zeros(8, dtype=torch.int32).pin_memory(), None] for _ in range(4)]
+            self._writer = BlockWriter(8)
             self._write()
         elif device is not None and torch.device(device).type == "cuda" and torch.device(device).index not in (None, self._block.device.index):
             raise RuntimeError(f"Mixup: the parameter block lives on {self._block.device}, the tensors on {device}")
@@ -152,17 +153,8 @@ class Mixup:
     def _write(self):
         if self._block is None:
             return
-        # an asynchronous copy from pinned memory on the current stream: ordered before the next launch / replay, and the
-        # host does not wait for the step in flight.  A staging buffer is rewritten only once its own last copy is done
-        # (four take turns, so that is the copy of four calls ago)
-        slot = self._host[self._turn]
-        self._turn = (self._turn + 1) % len(self._host)
-        if slot[1] is not None:
-            slot[1].synchronize()
-        slot[0].copy_(torch.frombuffer(bytearray(self.packed()), dtype=torch.int32))
-        self._block.copy_(slot[0], non_blocking=True)
-        slot[1] = torch.cuda.Event()
-        slot[1].record(torch.cuda.current_stream(self._block.device))
+        # an asynchronous copy from pinned memory on the current stream, no host wait (fastvim_amd/_devblock.py)
+        self._writer.write(self._block, self.packed())
 
     def _check_batch(self, x):
         if x.shape[0] % 2 != 0:

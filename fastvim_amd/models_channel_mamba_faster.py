@@ -20,9 +20,11 @@ from torch import Tensor
 
 from .fastvim import (DropPath, _compute_dtype, _init_weights, segm_init_weights as _segm_2d,
                       to_2tuple, trunc_normal_)
+from . import glue_ops as G
+from .hcs import draw as draw_channels, upload as upload_channels
 from .layernorm import RMSNorm, layer_norm_fn
 from .mamba_simple_channel_faster import Mamba
-from .mamba_simple_faster import LinearFn, linear_module
+from .mamba_simple_faster import LinearFn, _direct_grad, _shadow, linear_fwd, linear_module, linear_wgrad
 from .mixer_ops import reduce_partials
 
 
@@ -63,6 +65,70 @@ class _ChannelEmbedEpilogueFn(torch.autograd.Function):
         return g.to(ctx.lin_dtype), dbias, dchan, dpos
 
 
+class _ChanPatchProjFn(torch.autograd.Function):
+    """patches (B, P*C, K) -> fp32 (B, P*C, D) = round(patches @ W^T) + table, table[p*C + k] = (chan_w[sel[k]] + bias) +
+    pos[p]: the shared projection, the conv bias, the channel embedding of the selected channels and ``x +
+    repeat_interleave(pos_embed, C, 1)`` -- bit for bit ``LinearFn`` followed by ``_ChannelEmbedEpilogueFn`` on the
+    torch-gathered embedding.  bf16: ONE GEMM whose epilogue adds the table (``fv_gemm_bf16_rowbias``, period P*C), as
+    ``fastvim._PatchProjFn``; fp32: the GEMM and one add of the table.  ``sel``: the C channel indices in device memory
+    (None: the first C), read by the table kernel and by the scatter of backward when they run.  Backward takes
+    ``_ChannelEmbedEpilogueFn``'s fixed-order sums (batch first, then positions / channels), places the channel rows into
+    the (in_chans, D) gradient with ``fv_chan_embed_scatter`` -- rows of undrawn channels stay zero -- and sums straight
+    into the flat gradients where the parameters have them."""
+
+    @staticmethod
+    def forward(ctx, patches, W, bias, chan_w, pos, sel, n_sel, cdt):
+        B, Ltok, K = patches.shape
+        D, P = W.shape[0], Ltok // n_sel
+        with torch.autocast("cuda", enabled=False):
+            table = G.chan_embed_table(chan_w.detach().float().contiguous(),
+                                       None if bias is None else bias.detach().float().contiguous(),
+                                       None if pos is None else pos.detach().float().reshape(P, D).contiguous(), sel, n_sel, P)
+            a2, Wc = patches.view(B * Ltok, K), _shadow(W, cdt).reshape(D, K)
+            if cdt == torch.bfloat16 and K % 8 == 0 and D % 8 == 0:
+                y = G.gemm_rowbias(a2, Wc, table).view(B, Ltok, D)
+            else:
+                y = torch.add(table, linear_fwd(a2, Wc).view(B, Ltok, D))      # fp32 + compute dtype promotes to fp32
+        ctx.save_for_backward(patches, W, bias, chan_w, pos, sel)
+        ctx.cdt, ctx.n_sel = cdt, n_sel
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        patches, W, bias, chan_w, pos, sel = ctx.saved_tensors
+        B, Ltok, K = patches.shape
+        C, D = ctx.n_sel, W.shape[0]
+        P = Ltok // C
+        with torch.autocast("cuda", enabled=False):
+            g = g.contiguous()
+            dbias = dchan = dpos = None
+            per_tok = reduce_partials(g.view(B, Ltok * D), B).view(P, C * D)                  # sum over batch
+            d_cd = reduce_partials(per_tok, P).view(C, D)                                     # then over positions
+            if ctx.needs_input_grad[3]:
+                gd = _direct_grad(chan_w)
+                if gd is not None:
+                    G.chan_embed_scatter_(gd, d_cd, sel)
+                else:
+                    dchan = G.chan_embed_scatter_(torch.zeros(chan_w.shape, device=g.device, dtype=torch.float32), d_cd, sel)
+            if bias is not None and ctx.needs_input_grad[2]:
+                gd = _direct_grad(bias)
+                if gd is not None:
+                    reduce_partials(d_cd, C, out=gd.view(-1), accumulate=True)
+                else:
+                    dbias = reduce_partials(d_cd, C)                                          # ... and over channels
+            if pos is not None and ctx.needs_input_grad[4]:
+                by_c = per_tok.view(P, C, D).transpose(0, 1).contiguous().view(C, P * D)
+                gd = _direct_grad(pos)
+                if gd is not None:
+                    reduce_partials(by_c, C, out=gd.view(-1), accumulate=True)
+                else:
+                    dpos = reduce_partials(by_c, C).view(pos.shape)                           # sum over channels
+            dW = linear_wgrad(g.view(B * Ltok, D).to(ctx.cdt), patches.view(B * Ltok, K), W)
+            if dW is not None:
+                dW = dW.view(W.shape)
+        return None, dW, dbias, dchan, dpos, None, None, None
+
+
 class PatchEmbedPerChannel(nn.Module):
     """Per-channel patch embedding with a shared projection, a channel-embedding table and
     hierarchical channel sampling (models_channel_mamba_faster.py:22-203)."""
@@ -94,41 +160,64 @@ class PatchEmbedPerChannel(nn.Module):
         self.proj = nn.Conv3d(1, embed_dim, kernel_size=(1, patch_size, patch_size), stride=(1, stride, stride))
         self.channel_embed = nn.Embedding(in_chans, embed_dim)
 
-    def forward(self, x: Tensor, input_channel_order: Optional[Tensor] = None, pos_embed=None):
+    def forward(self, x: Tensor, input_channel_order: Optional[Tensor] = None, pos_embed=None, hcs=None):
         """Returns (tokens (B, P*C', D) Channel-First, C', h, w, channels) like the reference (:203).
-        ``pos_embed`` (1, P, D), optional: added (repeat-interleaved per channel) in the same epilogue."""
+        ``pos_embed`` (1, P, D), optional: added (repeat-interleaved per channel) in the same epilogue.
+        ``hcs`` (a ``fastvim_amd.hcs.ChannelSampler``), optional: in training mode with ``self.hcs`` the subset is the
+        sampler's current one -- the count from the host, the indices from its device array when the kernels run -- and
+        Python's ``random`` is not consumed here; without one the subset is drawn here, as the reference does."""
         B, num_channels, h, w = x.shape
-        if input_channel_order is None:
-            chan = self.channel_embed.weight[:num_channels][None]                # (1, C, D), == embedding(arange)
-        else:
-            chan = self.channel_embed(input_channel_order)                       # (B, C, D)
+        if hcs is not None and input_channel_order is not None:
+            raise NotImplementedError("PatchEmbedPerChannel: a ChannelSampler together with per-sample input_channel_order")
+        ph, pw = self.patch_size
+        gh, gw = h // ph, w // pw
+        g0, g1 = (gw, gh) if self.scanpath_type == "colwise" else (gh, gw)       # :193-194
+        cdt = _compute_dtype(x)
+        D = self.proj.weight.shape[0]
+        # the HIP embed: gather + unfold + cast in one launch, the per-token table, the GEMM.  Per-sample channel ids, an
+        # image that asks for its gradient (the unfold has no autograd node), CPU tensors and shapes outside the unfold's
+        # limits keep the strided-copy chain below
+        kernels = (input_channel_order is None and G.patch_unfold_chan_ok(x, ph, pw, num_channels)
+                   and cdt in (torch.float32, torch.bfloat16) and not (x.requires_grad and torch.is_grad_enabled())
+                   and num_channels <= self.channel_embed.weight.shape[0])
+        sel = None
         # same python-RNG consumption as the reference (:167-185)
         if self.training and self.hcs:
-            c_new = random.randint(1, num_channels)
-            channels = random.sample(range(num_channels), k=c_new)
-            if self.sort_channels is True:
-                channels.sort()
-            num_channels = c_new
-            x = x[:, channels, :, :]
-            chan = chan[:, channels]
+            if hcs is not None:
+                if hcs.num_channels != num_channels:
+                    raise ValueError(f"PatchEmbedPerChannel: the sampler draws from {hcs.num_channels} channels, the images have {num_channels}")
+                if not kernels:
+                    raise RuntimeError("PatchEmbedPerChannel: a ChannelSampler needs the HIP embed path (GPU images without "
+                                       "gradient, fp32 / bf16, patch width a multiple of 8)")
+                channels, sel = hcs.last(), hcs.block(x.device)
+            else:
+                channels = draw_channels(num_channels, self.sort_channels)
+                if kernels:
+                    sel = upload_channels(channels, x.device)
+            sampled = True
         else:
             channels = random.sample(range(num_channels), k=num_channels)
             channels.sort()
-        ph, pw = self.patch_size
-        gh, gw = h // ph, w // pw
-        C = num_channels
-        cdt = _compute_dtype(x)
-        p6 = x.reshape(B, C, gh, ph, gw, pw)
-        if self.scanpath_type == "colwise":                                      # :193-194
-            patches = p6.permute(0, 4, 2, 1, 3, 5)
-            g0, g1 = gw, gh
+            sampled = False
+        C = len(channels)
+        if kernels:
+            patches = G.patch_unfold_chan(x, ph, pw, cdt, sel, C, colwise=self.scanpath_type == "colwise")
+            out = _ChanPatchProjFn.apply(patches, self.proj.weight, self.proj.bias, self.channel_embed.weight, pos_embed,
+                                         sel, C, cdt).view(B, g0 * g1, C, D)
         else:
-            patches = p6.permute(0, 2, 4, 1, 3, 5)
-            g0, g1 = gh, gw
-        patches = patches.reshape(B, g0 * g1 * C, ph * pw)                       # (row, col, channel) order
-        lin = LinearFn.apply(patches, self.proj.weight, cdt)                     # weight viewed (D, ph*pw)
-        D = lin.shape[-1]
-        out = _ChannelEmbedEpilogueFn.apply(lin.view(B, g0 * g1, C, D), self.proj.bias, chan, pos_embed)
+            if input_channel_order is None:
+                chan = self.channel_embed.weight[:num_channels][None]            # (1, C, D), == embedding(arange)
+            else:
+                chan = self.channel_embed(input_channel_order)                   # (B, C, D)
+            if sampled:
+                x = x[:, channels, :, :]
+                chan = chan[:, channels]
+            p6 = x.reshape(B, C, gh, ph, gw, pw)
+            patches = p6.permute(0, 4, 2, 1, 3, 5) if self.scanpath_type == "colwise" else p6.permute(0, 2, 4, 1, 3, 5)
+            patches = patches.reshape(B, g0 * g1 * C, ph * pw)                   # (row, col, channel) order
+            lin = LinearFn.apply(patches, self.proj.weight, cdt)                 # weight viewed (D, ph*pw)
+            out = _ChannelEmbedEpilogueFn.apply(lin.view(B, g0 * g1, C, D), self.proj.bias, chan, pos_embed)
+        num_channels = C
         if self.scan_order == "Spatial-First":                                   # tokens ordered (channel, row, col)
             out = out.transpose(1, 2)                                            # (B, C, P, D); pos_embed[p] per (c, p) (:620-623)
             if self.flatten:
@@ -296,12 +385,14 @@ class VisionMamba(nn.Module):
 
     # forward_features (models_channel_mamba_faster.py:607-667) in the four pieces the segmented data-parallel step cuts at
     # (fastvim_amd/pipeline.py: gradient buckets exchanged under the backward of the remaining runs of blocks)
-    def _embed(self, x):
+    def _embed(self, x, hcs=None):
+        """``hcs`` (a ``fastvim_amd.hcs.ChannelSampler``), optional: the channel subset of a training forward is the
+        sampler's current one instead of a draw made here (``PatchEmbedPerChannel.forward``)."""
         if self.if_abs_pos_embed:
-            x, tokens_per_patch, h, w, _ = self.patch_embed(x, pos_embed=self.pos_embed)   # :617-627
+            x, tokens_per_patch, h, w, _ = self.patch_embed(x, pos_embed=self.pos_embed, hcs=hcs)   # :617-627
             x = self.pos_drop(x)
         else:
-            x, tokens_per_patch, h, w, _ = self.patch_embed(x)
+            x, tokens_per_patch, h, w, _ = self.patch_embed(x, hcs=hcs)
         self._tokens_per_patch = tokens_per_patch       # what every block of this forward pass is called with
         if self.training:
             DropPath.predraw([l.drop_path for l in self.layers] + [self.drop_path], x.shape[0], x.device)
@@ -338,13 +429,13 @@ class VisionMamba(nn.Module):
             x = x.max(dim=1)[0]
         return x
 
-    def forward_features(self, x, inference_params=None):
-        hidden_states, _ = self._embed(x)
+    def forward_features(self, x, inference_params=None, hcs=None):
+        hidden_states, _ = self._embed(x, hcs=hcs)
         hidden_states, residual = self._run_layers(hidden_states, None, 0, len(self.layers), inference_params)
         return self._final(hidden_states, residual)
 
-    def forward(self, x, return_features=False, inference_params=None):
-        x = self.forward_features(x, inference_params)
+    def forward(self, x, return_features=False, inference_params=None, hcs=None):
+        x = self.forward_features(x, inference_params, hcs=hcs)
         if return_features:
             return x
         return self._head(x)

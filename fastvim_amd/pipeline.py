@@ -33,13 +33,20 @@ class SegmentedTrainStep:
     the batch is mixed inside the step with the parameters of the last ``mixup.sample()``, which the caller issues between
     steps like ``opt.set_lr``:  ``x.copy_(batch); labels.copy_(y); mixup.sample(); opt.set_lr(lr); step.step()``.
 
+    ``hcs`` (a ``fastvim_amd.hcs.ChannelSampler``, for the channel models: ``model._embed`` must take ``hcs=``): hierarchical
+    channel sampling inside the step.  The caller draws between steps -- ``x.copy_(batch); target.copy_(y); hcs.sample();
+    opt.set_lr(lr); step.step()`` -- and the step embeds the sampler's current subset: the indices are read from its device
+    array when the kernels run, the COUNT fixes every shape downstream, so one family of forward / backward graphs is
+    captured per count 1..num_channels (largest first, into one memory pool: only one family runs at a time) and
+    ``step()`` replays the family of ``hcs.count``; the optimizer graph does not depend on the count and is shared.
+
     Capture needs ``warmup`` eager steps first (allocator, lazily built buffers, RCCL communicators).  They are real
     steps on whatever ``x`` / ``target`` hold, so the training state they touch -- parameters, bf16 shadow, Adam moments,
     EMA, step count, the CPU and GPU RNG streams -- is snapshotted before and put back after them: constructing the
     step object leaves the model, the optimizer and the DropPath stream exactly as it found them."""
 
     def __init__(self, model, flat, opt, loss_fn, x, target, n_segments=3, amp_dtype=torch.bfloat16, use_graph=True,
-                 warmup=2, mixup=None):
+                 warmup=2, mixup=None, hcs=None):
         self.model, self.flat, self.opt, self.loss_fn = model, flat, opt, loss_fn
         self.x, self.target, self.amp_dtype = x, target, amp_dtype
         # batch-mode Mixup / CutMix inside the step: the images are mixed on their way into the patch embedding by whatever
@@ -52,6 +59,13 @@ class SegmentedTrainStep:
             self._embed_takes_mix = "mix" in inspect.signature(model._embed).parameters
             if not self._embed_takes_mix:                # such a model gets the mixed batch from one fv_mix_batch launch
                 self._x_mixed = torch.empty_like(x, memory_format=torch.contiguous_format)
+        # hierarchical channel sampling: the subset of the sampler's device array, one family of graphs per channel count
+        self.hcs = hcs
+        if hcs is not None and "hcs" not in inspect.signature(model._embed).parameters:
+            raise TypeError("SegmentedTrainStep: hcs= needs a model whose _embed takes the sampler (`_embed(x, hcs=None)`: "
+                            "fastvim_amd.models_channel_mamba_faster.VisionMamba)")
+        if hcs is not None:
+            hcs.block(x.device)                          # the index array exists before any capture
         self.exchange = flat.make_exchange(n_segments)
         self.runs = self.exchange.layers                 # (lo, hi) block ranges in BACKWARD order
         self.K = len(self.runs)
@@ -62,7 +76,14 @@ class SegmentedTrainStep:
         self._cuts = None
         self._exposed = []                               # (event before finish, event after) of the timed steps
         self.graphs = None
+        self.families = None                             # with hcs: {count: (forward graph, backward graphs, loss tensor)}
         if use_graph:
+            pe = getattr(model, "patch_embed", None)
+            if hcs is None and model.training and getattr(pe, "hcs", False) is True:
+                warnings.warn("SegmentedTrainStep: the model samples channels (patch_embed.hcs) and no hcs= sampler was given: "
+                              "the subset drawn during capture is frozen into the graphs and every replay embeds it.  Pass "
+                              "hcs=fastvim_amd.hcs.ChannelSampler(channels) and call its sample() between steps.",
+                              RuntimeWarning, stacklevel=2)
             self._capture(warmup)
 
     # ------------------------------------------------------------------ the pieces
@@ -71,12 +92,13 @@ class SegmentedTrainStep:
         self.flat.zero_grad()
         cuts = []              # per run in FORWARD order: (inputs (leaves) or None, outputs)
         with torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.amp_dtype != torch.float32):
+            kw = {} if self.hcs is None else {"hcs": self.hcs}
             if self.mixup is None:
-                h, _ = m._embed(self.x)
+                h, _ = m._embed(self.x, **kw)
             elif self._embed_takes_mix:
-                h, _ = m._embed(self.x, mix=self.mixup)
-            else:
-                h, _ = m._embed(self.mixup.mix_batch(self.x, out=self._x_mixed))
+                h, _ = m._embed(self.x, mix=self.mixup, **kw)
+            else:              # (the channel models: the whole image is mixed before channels are selected, the reference's order)
+                h, _ = m._embed(self.mixup.mix_batch(self.x, out=self._x_mixed), **kw)
             res, pend = None, None
             fwd_runs = self.runs[::-1]
             open_runs = hasattr(m, "_run_layers_open")
@@ -136,16 +158,18 @@ class SegmentedTrainStep:
             if torch.is_tensor(v) and v.is_cuda and all(v is not b for b in bufs):
                 bufs.append(v)
         dev = f.param_flat.device
-        return ([(b, b.clone()) for b in bufs], torch.get_rng_state(), torch.cuda.get_rng_state(dev), dev)
+        return ([(b, b.clone()) for b in bufs], torch.get_rng_state(), torch.cuda.get_rng_state(dev), dev,
+                None if self.hcs is None else self.hcs.last())
 
-    @staticmethod
-    def _restore(snap):
-        bufs, cpu_rng, gpu_rng, dev = snap
+    def _restore(self, snap, sampler=True):
+        bufs, cpu_rng, gpu_rng, dev, subset = snap
         with torch.no_grad():
             for b, saved in bufs:
                 b.copy_(saved)
         torch.set_rng_state(cpu_rng)
         torch.cuda.set_rng_state(gpu_rng, dev)
+        if subset is not None and sampler:
+            self.hcs.set(subset)
 
     def _capture(self, warmup):
         from . import graph_capture_safe
@@ -158,15 +182,6 @@ class SegmentedTrainStep:
             self.use_graph = False
             return
         snap = self._snapshot()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._eager_step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self._restore(snap)
-        torch.cuda.synchronize()
         pool = torch.cuda.graph_pool_handle()
         # With a process group alive, its watchdog THREAD polls the events of finished collectives (hipEventQuery); under the
         # default "global" capture mode any thread's event query while this thread captures is an error
@@ -174,15 +189,39 @@ class SegmentedTrainStep:
         # down, intermittently, in tests/test_pipeline_gpu.py::test_rccl_buckets_between_backward_graphs).  "thread_local"
         # restricts the check to the capturing thread, which issues nothing but kernel launches.
         mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-        g_fwd = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g_fwd, pool=pool, capture_error_mode=mode):
-            self.loss = self._forward()
-        g_bwd = []
-        for k in range(self.K):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=mode):
-                self._backward(k)
-            g_bwd.append(g)
+
+        def family():
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(warmup):
+                    self._eager_step()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            self._restore(snap, sampler=False)           # (a family keeps the subset it was warmed up with for its capture)
+            torch.cuda.synchronize()
+            g_fwd = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g_fwd, pool=pool, capture_error_mode=mode):
+                loss = self._forward()
+            g_bwd = []
+            for k in range(self.K):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, pool=pool, capture_error_mode=mode):
+                    self._backward(k)
+                g_bwd.append(g)
+            return g_fwd, g_bwd, loss
+
+        if self.hcs is None:
+            g_fwd, g_bwd, self.loss = family()
+        else:
+            # one family per channel count, the largest first (it sizes the shared pool); each is warmed up and captured with
+            # the first c channels in the array -- a replay reads whatever the array holds then
+            self.families = {}
+            for c in range(self.hcs.num_channels, 0, -1):
+                self.hcs.set(range(c))
+                self.families[c] = family()
+            self.hcs.set(snap[4])                        # the sampler's own selection again
+            g_fwd, g_bwd, self.loss = self.families[self.hcs.count]
         g_opt = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g_opt, pool=pool, capture_error_mode=mode):
             self.opt.step(grad_scale=self._gscale)
@@ -195,6 +234,8 @@ class SegmentedTrainStep:
             self.loss = self._eager_step()
             return self.loss
         g_fwd, g_bwd, g_opt = self.graphs
+        if self.families is not None:                    # the family of the sampler's current count
+            g_fwd, g_bwd, self.loss = self.families[self.hcs.count]
         g_fwd.replay()
         for k in range(self.K):
             g_bwd[k].replay()

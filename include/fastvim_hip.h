@@ -48,7 +48,9 @@ const char* fv_last_error(void);
  *      fv_mixer_combine_out_proj_addnorm_pk were ADDED (projection weights streamed in MFMA fragment order); the plain
  *      entry points keep their signatures and the plain layout.
  *      Later, still 3: fv_mix_batch, fv_patch_unfold_mix, fv_mixup_target and fv_label_ce were ADDED (batch Mixup /
- *      CutMix and the losses on integer labels). */
+ *      CutMix and the losses on integer labels).
+ *      Later, still 3: fv_patch_unfold_chan, fv_chan_embed_table and fv_chan_embed_scatter were ADDED (hierarchical
+ *      channel sampling of the channel models with the drawn subset in device memory). */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -639,6 +641,35 @@ int fv_mixup_target(const int64_t* labels, float* target, int batch, int classes
 int fv_label_ce(const void* logits, int logits_dtype, const int64_t* labels, const void* mix, double smoothing,
                 float* loss_rows, float* loss, float* dlogits, int32_t* correct_rows, int32_t* n_correct, int batch,
                 int classes, fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Hierarchical channel sampling of the channel models (PatchEmbedPerChannel.forward,
+ * models/channel_wise_tokenization/models_channel_mamba_faster.py:167-181): every training forward embeds a drawn
+ * subset of n_sel of the image's chans_total channels.  The COUNT n_sel fixes every shape downstream and is a launch
+ * argument; the INDICES are read from `sel`, n_sel int32 in device memory, when the kernel runs -- the host rewrites
+ * them between two replays of a captured launch, like the mix-parameter block.  sel == NULL is the identity
+ * (channels 0 .. n_sel-1: evaluation, hcs off).  An index outside [0, chans_total) is clamped into it by the gather
+ * kernels and skipped by the scatter; the indices of a subset are distinct.
+ * ---------------------------------------------------------------------- */
+/* The per-channel patches of the shared Conv3d(1, D, (1, ph, pw)) projection (:117-125) as a GEMM operand, in
+ * (row, col, channel) token order (:193-198), unfolded, gathered and cast in one pass:
+ *   out[b][(p * n_sel + k)][pi*pw + pj] = img[b][sel[k]][gi*ph + pi][gj*pw + pj],
+ *   p = gi*gw + gj, or gj*gh + gi with `colwise` (scanpath_type == "colwise", :193-194).
+ * img (batch, chans_total, height, width), out (batch, gh*gw*n_sel, ph*pw); fp32 or bf16 each; pw % 8 == 0.  Every
+ * byte of a selected channel is read once, an unselected channel is not touched, the gathered image never exists. */
+int fv_patch_unfold_chan(const void* img, int img_dtype, void* out, int out_dtype, int batch, int chans_total,
+                         int height, int width, int ph, int pw, const int32_t* sel, int n_sel, int colwise,
+                         fv_stream_t stream);
+/* The per-token table fv_gemm_bf16_rowbias adds (period = positions * n_sel), fp32, in exactly this association:
+ *   table[p * n_sel + k][:] = (chan_table[sel[k]][:] + bias[:]) + pos[p][:]
+ * chan_table (chans_total, dim) -- the channel embedding (:188-191); bias (dim) and pos (positions, dim) -- the conv
+ * bias and x + repeat_interleave(pos_embed, n_sel, 1) (:626-627) -- may each be NULL (that term is left out). */
+int fv_chan_embed_table(const float* chan_table, const float* bias, const float* pos, float* table, const int32_t* sel,
+                        int n_sel, int chans_total, int positions, int dim, fv_stream_t stream);
+/* The adjoint of the table's gather: d_table[sel[k]][:] += d_chan[k][:], d_chan (n_sel, dim), d_table (chans_total, dim),
+ * fp32.  The rows of channels that were not drawn are not touched.  One thread owns an element: no atomics. */
+int fv_chan_embed_scatter(const float* d_chan, float* d_table, const int32_t* sel, int n_sel, int chans_total, int dim,
+                          fv_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Fused AdamW (decoupled weight decay, bias correction; torch.optim.AdamW semantics) over a flat fp32
