@@ -32,6 +32,7 @@ C_ABI_SYMBOLS = (
     "fv_pack_weight_frags_batched", "fv_mixer_conv_pool_bwd_dgrad_pk", "fv_mixer_combine_out_proj_addnorm_pk",
     "fv_mix_batch", "fv_patch_unfold_mix", "fv_mixup_target", "fv_label_ce",
     "fv_patch_unfold_chan", "fv_chan_embed_table", "fv_chan_embed_scatter",
+    "fv_mixer_plan",
 )
 
 

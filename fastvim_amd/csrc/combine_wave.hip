@@ -17,7 +17,7 @@ namespace {
 using fvi::BwdParams;
 using fvi::FwdParams;
 
-constexpr int NW = 4;     // waves (= groups in flight) per block
+constexpr int NW = fvplan::WAVE_NW;     // waves (= groups in flight) per block
 
 __device__ __forceinline__ float hsum(f2 v) { return v.x + v.y; }
 
@@ -296,23 +296,12 @@ __global__ __launch_bounds__(64 * NW) void combine_bwd_wave_kernel(BwdParams p) 
   for (int e = threadIdx.x; e < 2 * p.d_in; e += blockDim.x) dst[e] = smem[e];
 }
 
-int mode() {   // tuning hook: 0 = generic kernels only, 1 = wave kernels where a token spans more than one 384-chunk, 2 = wherever they apply
-  static const int m = fv_tune("FASTVIM_COMBINE_WAVE", 2);
-  return m;
-}
-
-int chunks(int d_in) {
-  if (d_in % 384 != 0 || d_in / 384 > 2) return 0;
-  const int nck = d_in / 384;
-  return (mode() >= 2 || (mode() == 1 && nck > 1)) ? nck : 0;
-}
+inline int mode() { return fvplan::combine_wave_mode(); }
+inline int chunks(int d_in) { return fvplan::combine_wave_chunks(d_in); }
 
 }  // namespace
 
-static bool wide_bwd(int d_in) {
-  static const bool on = (fv_tune("FASTVIM_COMBINE_WAVE_B", 1) != 0);   // tuning hook
-  return on && d_in == 4 * 384 && mode() >= 1;
-}
+static bool wide_bwd(int d_in) { return fvplan::combine_wave_wide_bwd(d_in); }
 
 int fvi::combine_wave_blocks(int B, int rows, int tpp, int d_in) {
   if (!chunks(d_in) && !wide_bwd(d_in)) return 0;
@@ -326,7 +315,7 @@ int fvi::combine_wave_blocks(int B, int rows, int tpp, int d_in) {
 #define FV_WAVE_LAUNCH(KERNEL, PARAMS, SMEM)                                                        \
   do {                                                                                             \
     const int nck = chunks(p.d_in);                                                                \
-    if (!nck) return FV_ERR_UNSUPPORTED;                                                           \
+    FV_CHECK(nck, "mixer_combine: not a wave-per-token plan");                                                       \
     FV_CHECK((size_t)p.geo.L * 2 * p.d_in * 4 <= 0xfffff000ull,                                    \
              "mixer_combine: %d tokens x %d channels exceed the 32-bit buffer offsets of the wave kernels", p.geo.L, p.d_in); \
     const dim3 grid(fvi::combine_wave_blocks(p.B, p.geo.rows, p.geo.tpp, p.d_in)), block(64 * NW); \

@@ -504,58 +504,21 @@ int launch_row(const BwdParams& p, int nch, int rgr, int grid, int groups, size_
 
 }  // namespace
 
-int fvi::conv_pool_bwd_row(const BwdParams& p, int nch, int rg, int grid, size_t smem, int dtype, hipStream_t st) {
-  // nch counts 128-channel waves (a lane owns a channel pair)
-  if (p.d_in != nch * 128) return FV_ERR_UNSUPPORTED;
-  if ((size_t)p.geo.L * 2 * p.d_in * 4 > 0xfffff000ull) return FV_ERR_UNSUPPORTED;   // one batch element per descriptor
-  if ((size_t)p.B * p.geo.rows * p.d_in * 8 > 0x7ffff000ull) return FV_ERR_UNSUPPORTED;   // pooled gradients: one descriptor, int offsets
-  const bool chan8 = p.geo.tpp == 8 && p.geo.pcols >= 2;
-  const bool dense8 = p.geo.tpp == 1 && p.geo.cols % 8 == 0 && p.geo.cols >= 24;      // 512 / 1024 / 2048 px grids
-  const bool long_rows = chan8 || dense8;
-  if (p.dxc2 && (long_rows || p.geo.tpp != 1 || (p.geo.cols != 14 && p.geo.cols != 16))) return FV_ERR_UNSUPPORTED;
-  // channel groups over blockIdx.y.  Long-row kernels (201 VGPRs: 8 waves per CU): blocks of FOUR waves -- at most two waves of channels x two or four rows -- so that two
-  // blocks share a CU and the dispatcher has 2-6x as many, lighter blocks to balance (six-wave blocks left a quarter of
-  // the wave slots empty): FastChannelVim-S 200.5 -> 173 us, FastVim-B at 2048 px 448.7 -> 385 us
-  // (profiles/r05_ab_chan_block_shapes.log)
-  static const int t_groups = fv_tune("FASTVIM_BWD_CHAN_GROUPS", 0), t_rg = fv_tune("FASTVIM_BWD_CHAN_RG", 0);   // tuning hooks
-  // rows live in registers: whole-row blocks of <= 512 threads (256 VGPRs per wave) for fp32 storage and 16-token rows,
-  // <= 768 (168) for the bf16 14-token kernel, i.e. fewer row groups per block than the generic kernel, over the same
-  // persistent grid.  The split must not leave wave slots of the CU empty (FastVim-B, 12 waves of channels: two
-  // 6-wave blocks 99.5 us, one 12-wave block 73.4, three 4-wave blocks 75.6)
-  const int wmax = (long_rows || dtype == FV_F32 || p.geo.cols > 14) ? 8 : 12;
-  int groups = 1, nchg = nch, rgr = 1;
-  if (long_rows) {
-    groups = (nch + 1) / 2;
-    while (nch % groups) ++groups;
-    if (t_groups > 0 && nch % t_groups == 0) groups = t_groups;
-    nchg = nch / groups;
-    rgr = t_rg > 0 ? t_rg : 4 / nchg;
-    smem = (size_t)12 * nchg * 128 * 4;           // a block accumulates its own channels only
-    if (chan8) smem += (size_t)nchg * rgr * ((2 * 3 + 2 * 8) * 64) * 8;      // + the waves' parked slot gradients (11 KB per wave)
-  } else {
-    static const int r_groups = fv_tune("FASTVIM_BWD_ROW_GROUPS", 0), r_rg = fv_tune("FASTVIM_BWD_ROW_RG", 0);   // tuning hooks
-    for (groups = 1; groups <= nch; ++groups) {
-      if (nch % groups) continue;
-      nchg = nch / groups;
-      if (nchg > wmax) continue;
-      rgr = rg < wmax / nchg ? rg : wmax / nchg;
-      if (wmax % (nchg * rgr) == 0) break;
-    }
-    if (groups > nch) { groups = nch; nchg = 1; rgr = 1; }
-    if (r_groups > 0 && nch % r_groups == 0) { groups = r_groups; nchg = nch / groups; rgr = rg < wmax / nchg ? rg : (wmax / nchg < 1 ? 1 : wmax / nchg); }
-    if (r_rg > 0) rgr = r_rg;
-  }
-  if (chan8 || dense8) {
-    static const bool chan = (fv_tune("FASTVIM_BWD_CHAN", 1) != 0);   // tuning hook
-    if (!chan) return FV_ERR_UNSUPPORTED;
+int fvi::conv_pool_bwd_row(const BwdParams& p, const fvplan::Plan& pl, int grid, int dtype, hipStream_t st) {
+  // channel groups over blockIdx.y, waves of 128 channels (a lane owns a channel pair) and row groups per block:
+  // fvplan::conv_pool_bwd_row_split (mixer_plan.h)
+  const int groups = pl.slabs, nchg = pl.waves, rgr = pl.row_groups;
+  const size_t smem = pl.lds_bytes;
+  FV_CHECK(p.d_in == groups * nchg * 128, "mixer_conv_pool_bwd: plan does not cover d_inner %d", p.d_in);
+  if (pl.form == fvplan::CELL) {
+    const bool chan8 = p.geo.tpp == 8;
+    FV_CHECK(!p.dxc2, "mixer_conv_pool_bwd2: the cell-walking kernels take no second pooled-gradient addend");
 #define FV_CH(TT, CC) launch_chan<TT, 8, CC>(p, nchg, rgr, grid, groups, smem, st)
     if (dtype == FV_F32) return chan8 ? FV_CH(float, true) : FV_CH(float, false);
     return chan8 ? FV_CH(bf16_t, true) : FV_CH(bf16_t, false);
 #undef FV_CH
   }
-  if (p.geo.tpp != 1 || (p.geo.cols != 14 && p.geo.cols != 16)) return FV_ERR_UNSUPPORTED;
-  static const bool wide = (fv_tune("FASTVIM_BWD_ROWK_WIDE", 1) != 0);   // tuning hook
-  if (groups > 1 && !wide) return FV_ERR_UNSUPPORTED;
+  FV_CHECK(pl.form == fvplan::ROW && p.geo.tpp == 1 && (p.geo.cols == 14 || p.geo.cols == 16), "mixer_conv_pool_bwd: not a whole-row plan");
   if (dtype == FV_F32)
     return p.geo.cols == 14 ? launch_row<float, 14>(p, nchg, rgr, grid, groups, smem, st)
                             : launch_row<float, 16>(p, nchg, rgr, grid, groups, smem, st);

@@ -212,23 +212,10 @@ __global__ __launch_bounds__(512) void conv_pool_fwd_chan_kernel(FwdParams p) {
   }
 }
 
-// channel groups: the smallest split of d_in / 128 waves into blocks of at most 2 waves.  The waves of a block share
-// nothing (each owns 128 channels of the row), so small blocks only help the dispatcher fill the CUs: FastChannelVim-S
-// (6 waves of channels) 101.1 us with one 6-wave block per row, 86.9 with three 2-wave blocks; FastVim-B at 2048 px
-// (12 waves) 239.6 -> 195.7 us (profiles/r05_ab_chan_block_shapes.log)
-inline int chan_groups(int d_in) {
-  const int nw = d_in / 128;
-  int gq = (nw + 1) / 2;
-  while (nw % gq) ++gq;
-  return gq;
-}
-
+// channel groups over blockIdx.z: fvplan::fwd_cell_groups / fwd_row_groups (mixer_plan.h)
 template <typename T, int TPP, bool CHAN>
-int launch_chan(const FwdParams& p, int pool_max, hipStream_t st) {
-  static const int t_gq = fv_tune("FASTVIM_FWD_CHAN_GROUPS", 0);   // tuning hook
-  const int nw = p.d_in / 128;
-  const int gq = (t_gq > 0 && nw % t_gq == 0) ? t_gq : chan_groups(p.d_in), nch = nw / gq;
-  dim3 grid(p.geo.rows, p.B, gq), block(64 * nch);
+int launch_chan(const FwdParams& p, const fvplan::Plan& pl, int pool_max, hipStream_t st) {
+  dim3 grid(p.geo.rows, p.B, pl.slabs), block(64 * pl.waves);
   if (pool_max) hipLaunchKernelGGL((conv_pool_fwd_chan_kernel<T, TPP, true, CHAN>), grid, block, 0, st, p);
   else hipLaunchKernelGGL((conv_pool_fwd_chan_kernel<T, TPP, false, CHAN>), grid, block, 0, st, p);
   FV_LAUNCH_CHECK();
@@ -236,45 +223,31 @@ int launch_chan(const FwdParams& p, int pool_max, hipStream_t st) {
 }
 
 template <typename T, int NT, int NP>
-int launch_row(const FwdParams& p, int pool_max, hipStream_t st) {
-  static const int t_gq = fv_tune("FASTVIM_FWD_ROW_GROUPS", 0);   // tuning hook
-  // blocks of at most 4 waves (channel groups over blockIdx.z), like the long-row kernel: FastVim-B 46.4 -> 43.2 us,
-  // FastVim-T (3 waves) unchanged
-  const int nw = p.d_in / (128 * NP);
-  int gq = (nw + 3) / 4;
-  while (nw % gq) ++gq;
-  if (t_gq > 0 && nw % t_gq == 0) gq = t_gq;
-  const int nch = nw / gq;
-  dim3 grid(p.geo.rows, p.B, gq), block(64 * nch);
+int launch_row(const FwdParams& p, const fvplan::Plan& pl, int pool_max, hipStream_t st) {
+  dim3 grid(p.geo.rows, p.B, pl.slabs), block(64 * pl.waves);
   if (pool_max) hipLaunchKernelGGL((conv_pool_fwd_row_kernel<T, NT, NP, true>), grid, block, 0, st, p);
   else hipLaunchKernelGGL((conv_pool_fwd_row_kernel<T, NT, NP, false>), grid, block, 0, st, p);
   FV_LAUNCH_CHECK();
   return FV_OK;
 }
 
+// one channel pair per lane up to d_inner 3072 (the channel groups ride on blockIdx.z); two pairs per lane only under
+// the tuning hook.  (Three pairs per lane spilled 26-62 registers at 256 and served no model: not built.)
 template <typename T, int NT>
-int pick_np(const FwdParams& p, int pool_max, hipStream_t st) {
-  static const int force = fv_tune("FASTVIM_FWD_NP", 0);   // tuning hook
-  // one channel pair per lane measured fastest (12.8 vs 16.5 us with three pairs on FastVim-T): more, shorter waves
-  if ((force == 0 || force == 1) && p.d_in % 128 == 0 && p.d_in <= 16 * 128) return launch_row<T, NT, 1>(p, pool_max, st);
-  // (three pairs per lane -- d_inner 2304 ... 3072 only -- spilled 26-62 registers at 256 and served no model: those widths
-  //  take the generic kernel)
-  if ((force == 0 || force == 2) && p.d_in % 256 == 0 && p.d_in <= 8 * 256) return launch_row<T, NT, 2>(p, pool_max, st);
-  return FV_ERR_UNSUPPORTED;
+int pick_np(const FwdParams& p, const fvplan::Plan& pl, int pool_max, hipStream_t st) {
+  return pl.vec == 2 ? launch_row<T, NT, 1>(p, pl, pool_max, st) : launch_row<T, NT, 2>(p, pl, pool_max, st);
 }
 
 }  // namespace
 
-int fvi::conv_pool_fwd_row(const FwdParams& p, int pool_max, int dtype, hipStream_t st) {
-  const bool fits = p.d_in % 128 == 0 && (size_t)p.geo.L * 2 * p.d_in * 4 <= 0xfffff000ull;   // one batch element per descriptor
-  static const bool chan = (fv_tune("FASTVIM_FWD_CHAN", 1) != 0);   // tuning hook
-  if (chan && fits && !pool_max && p.geo.tpp == 8 && p.geo.pcols >= 2 && p.d_in <= 8 * 128)
-    return dtype == FV_F32 ? launch_chan<float, 8, true>(p, pool_max, st) : launch_chan<bf16_t, 8, true>(p, pool_max, st);
-  // long rows of the dense path (cols = 32 / 64 / 128: the 512 / 1024 / 2048 px grids)
-  if (chan && fits && !pool_max && p.geo.tpp == 1 && p.geo.cols % 8 == 0 && p.geo.cols >= 24)
-    return dtype == FV_F32 ? launch_chan<float, 8, false>(p, pool_max, st) : launch_chan<bf16_t, 8, false>(p, pool_max, st);
-  if (p.geo.tpp != 1 || (p.geo.cols != 14 && p.geo.cols != 16)) return FV_ERR_UNSUPPORTED;
-  if (!fits) return FV_ERR_UNSUPPORTED;
-  if (dtype == FV_F32) return p.geo.cols == 14 ? pick_np<float, 14>(p, pool_max, st) : pick_np<float, 16>(p, pool_max, st);
-  return p.geo.cols == 14 ? pick_np<bf16_t, 14>(p, pool_max, st) : pick_np<bf16_t, 16>(p, pool_max, st);
+int fvi::conv_pool_fwd_row(const FwdParams& p, const fvplan::Plan& pl, int pool_max, int dtype, hipStream_t st) {
+  if (pl.form == fvplan::CELL) {
+    // channel-wise tokenization (tokens_per_patch 8), or long rows of the dense path (cols = 32 / 64 / 128)
+    if (p.geo.tpp == 8)
+      return dtype == FV_F32 ? launch_chan<float, 8, true>(p, pl, pool_max, st) : launch_chan<bf16_t, 8, true>(p, pl, pool_max, st);
+    return dtype == FV_F32 ? launch_chan<float, 8, false>(p, pl, pool_max, st) : launch_chan<bf16_t, 8, false>(p, pl, pool_max, st);
+  }
+  FV_CHECK(pl.form == fvplan::ROW && p.geo.tpp == 1 && (p.geo.cols == 14 || p.geo.cols == 16), "mixer_conv_pool_fwd: not a whole-row plan");
+  if (dtype == FV_F32) return p.geo.cols == 14 ? pick_np<float, 14>(p, pl, pool_max, st) : pick_np<float, 16>(p, pl, pool_max, st);
+  return p.geo.cols == 14 ? pick_np<bf16_t, 14>(p, pl, pool_max, st) : pick_np<bf16_t, 16>(p, pl, pool_max, st);
 }

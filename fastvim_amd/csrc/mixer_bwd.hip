@@ -24,7 +24,7 @@ constexpr int RGMAX = 4;   // a block walks up to RGMAX pooling rows concurrentl
 // Reads dg, z, skip once, writes dz and d_o once: 5 full-length tensors of traffic, no conv recompute
 // (xhat = ((yc_f + yc_b + skip)/2 - mean) * rstd is two FMAs from what the forward saved).  Block = RG row groups x NCH waves; a row group walks one pooling row.
 template <typename T, int VEC, int TT, bool TP>
-__global__ __launch_bounds__(VEC == 1 ? 1024 : 512) void combine_bwd_kernel(BwdParams p, int nch, int RG) {
+__global__ __launch_bounds__(VEC == 1 ? 1024 : VEC == 8 ? 320 : 512) void combine_bwd_kernel(BwdParams p, int nch, int RG) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform: row/token index math stays on the scalar unit
@@ -223,7 +223,8 @@ __global__ __launch_bounds__(VEC == 1 ? 1024 : 768) void conv_pool_bwd_kernel(Bw
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform (scalar index math)
   const int rg = wv / nch, cw = wv - rg * nch;
-  const int c0 = (cw * 64 + lane) * VEC;
+  const int c_lo = blockIdx.y * nch * 64 * VEC;          // channel slabs over blockIdx.y (d_inner 2048, 2560: two slabs)
+  const int c0 = c_lo + (cw * 64 + lane) * VEC;
   const bool act = c0 < p.d_in;
   const Geo g = p.geo;
   ChanParams<VEC> cp;
@@ -411,29 +412,43 @@ __global__ __launch_bounds__(VEC == 1 ? 1024 : 768) void conv_pool_bwd_kernel(Bw
       }
     }
   }
-  // one partial row per block: [d w (d_in*4) | d w_b (d_in*4) | d b | d b_b | dD | dD_b]
-  const int D = p.d_in;
+  // one partial row per block: [d w (d_in*4) | d w_b (d_in*4) | d b | d b_b | dD | dD_b]; a block accumulates the nc
+  // channels of its slab (all of them without slabs) and writes only their entries of the row
+  const int D = p.d_in, nc = gridDim.y == 1 ? D : nch * 64 * VEC;
   for (int r = 0; r < RG; ++r) {
     __syncthreads();
     if (r == rg && act) {
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
-        const int c = c0 + v;
+        const int c = c0 - c_lo + v;
 #pragma unroll
         for (int k = 0; k < CW; ++k) {
           smem[c * 4 + k] = (r == 0 ? 0.f : smem[c * 4 + k]) + a_wf[v][k];
-          smem[4 * D + c * 4 + k] = (r == 0 ? 0.f : smem[4 * D + c * 4 + k]) + a_wb[v][k];
+          smem[4 * nc + c * 4 + k] = (r == 0 ? 0.f : smem[4 * nc + c * 4 + k]) + a_wb[v][k];
         }
-        smem[8 * D + c] = (r == 0 ? 0.f : smem[8 * D + c]) + a_bf[v];
-        smem[9 * D + c] = (r == 0 ? 0.f : smem[9 * D + c]) + a_bb[v];
-        smem[10 * D + c] = (r == 0 ? 0.f : smem[10 * D + c]) + a_Df[v];
-        smem[11 * D + c] = (r == 0 ? 0.f : smem[11 * D + c]) + a_Db[v];
+        smem[8 * nc + c] = (r == 0 ? 0.f : smem[8 * nc + c]) + a_bf[v];
+        smem[9 * nc + c] = (r == 0 ? 0.f : smem[9 * nc + c]) + a_bb[v];
+        smem[10 * nc + c] = (r == 0 ? 0.f : smem[10 * nc + c]) + a_Df[v];
+        smem[11 * nc + c] = (r == 0 ? 0.f : smem[11 * nc + c]) + a_Db[v];
       }
     }
   }
   __syncthreads();
   float* dst = p.part + (size_t)blockIdx.x * 12 * D;
-  for (int e = threadIdx.x; e < 12 * D; e += blockDim.x) dst[e] = smem[e];
+  if (gridDim.y == 1) {
+    for (int e = threadIdx.x; e < 12 * D; e += blockDim.x) dst[e] = smem[e];
+  } else {
+    for (int e = threadIdx.x; e < 12 * nc; e += blockDim.x) {
+      int gi;
+      if (e < 4 * nc) gi = c_lo * 4 + e;
+      else if (e < 8 * nc) gi = 4 * D + c_lo * 4 + (e - 4 * nc);
+      else {
+        const int q = (e - 8 * nc) / nc, r = (e - 8 * nc) - q * nc;
+        gi = (8 + q) * D + c_lo + r;
+      }
+      dst[gi] = smem[e];
+    }
+  }
 }
 
 // out[i] = sum_s in[s*n + i] in a fixed order.  Block = 32 outputs x 8 row-slices: slice q sums rows
@@ -506,14 +521,6 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
   }
 }
 
-int rg_combine(int d_in, int VEC) { int nch = fv_cdiv(d_in, 64 * VEC); int r = 8 / nch; return r < 1 ? 1 : (r > RGMAX ? RGMAX : r); }
-int rg_convpool(int d_in, int VEC) { int nch = fv_cdiv(d_in, 64 * VEC); int r = (VEC == 1 ? 16 : 12) / nch; return r < 1 ? 1 : (r > RGMAX ? RGMAX : r); }
-int vec_combine(int d_in, int tpp) {
-  if (tpp > 1)      // LDS slot accumulators: keep the per-lane state small
-    return (d_in % 128 == 0 && d_in <= 8 * 128) ? 2 : (d_in % 256 == 0 && d_in <= 8 * 256) ? 4 : 1;
-  return (d_in % 384 == 0 && d_in <= 8 * 384) ? 6 : (d_in % 256 == 0 && d_in <= 8 * 256) ? 4 : 1;
-}
-int vec_convpool(int d_in) { return (d_in % 128 == 0 && d_in <= 12 * 128) ? 2 : 1; }
 int persistent_blocks(long nrows, int rg) {
   long groups = (nrows + rg - 1) / rg;
   // at most one block per CU: measured best for the persistent backward kernels (conv_pool_bwd at FastVim-T 32.6 us with 256
@@ -532,9 +539,11 @@ int persistent_blocks(long nrows, int rg) {
 // block per CU in x: FastChannelVim-S (896 rows, 3 groups) 224 x 3 blocks x 2 iterations = 2 rounds x 2 -> 150 x 3 x 3 =
 // 1 round x 3; 177 -> 166 us (profiles/r05_hook_sweep_final_tree.log).  Everything else: persistent_blocks.
 int conv_pool_bwd_blocks(long nrows, int d_in, int tpp) {
-  const int VEC = vec_convpool(d_in), rg = rg_convpool(d_in, VEC);
+  int VEC, slabs;
+  fvplan::conv_pool_bwd_vec(d_in, VEC, slabs);
+  const int rg = fvplan::conv_pool_bwd_grid_rg(d_in);
   const int base = persistent_blocks(nrows, rg);
-  if (tpp != 8 || VEC != 2 || d_in % 128) return base;
+  if (tpp != 8 || VEC != 2 || slabs != 1 || d_in % 128) return base;
   const int nch = d_in / 128;
   int groups = (nch + 1) / 2;
   while (nch % groups) ++groups;
@@ -546,36 +555,29 @@ int conv_pool_bwd_blocks(long nrows, int d_in, int tpp) {
   return cost(one_round) < cost(base) ? (int)one_round : base;
 }
 
-template <typename T, int VEC>
-int launch_combine_bwd(const BwdParams& p, hipStream_t st) {
-  const int nch = fv_cdiv(p.d_in, 64 * VEC);
-  FV_CHECK(nch <= (VEC == 1 ? 16 : 8), "mixer_combine_bwd: d_inner %d too large for the VEC=%d row walker", p.d_in, VEC);
-  const int rg = rg_combine(p.d_in, VEC);
+template <typename T, int VEC, bool TPOK = true>
+int launch_combine_bwd(const BwdParams& p, const fvplan::Plan& pl, hipStream_t st) {
+  const int nch = pl.waves, rg = pl.row_groups;
   dim3 grid(persistent_blocks((long)p.B * p.geo.rows, rg)), block(64 * nch * rg);
-  const size_t extra = (p.geo.tpp > 1 && p.geo.pcols > 1) ? (size_t)p.geo.tpp * 64 * nch * rg * VEC : 0;
-  FV_CHECK((RGMAX * 64 + 2 * p.d_in + extra) * 4 <= 64 * 1024, "mixer_combine_bwd: tokens_per_patch %d too large", p.geo.tpp);
+  const size_t smem = pl.lds_bytes;
   const bool tp = p.geo.tpp > 1;
+  if constexpr (!TPOK) FV_CHECK(!tp, "mixer_combine_bwd: %d channels per lane serve tokens_per_patch 1 only", VEC);
   if (p.geo.cols % 2 == 0) {
-    size_t smem = (size_t)(RGMAX * 2 * 2 * 16 + 2 * p.d_in + extra) * 4;
-    if (tp) hipLaunchKernelGGL((combine_bwd_kernel<T, VEC, 2, true>), grid, block, smem, st, p, nch, rg);
-    else hipLaunchKernelGGL((combine_bwd_kernel<T, VEC, 2, false>), grid, block, smem, st, p, nch, rg);
+    if constexpr (TPOK) if (tp) hipLaunchKernelGGL((combine_bwd_kernel<T, VEC, 2, true>), grid, block, smem, st, p, nch, rg);
+    if (!tp) hipLaunchKernelGGL((combine_bwd_kernel<T, VEC, 2, false>), grid, block, smem, st, p, nch, rg);
   } else {
-    size_t smem = (size_t)(RGMAX * 2 * 1 * 16 + 2 * p.d_in + extra) * 4;
-    if (tp) hipLaunchKernelGGL((combine_bwd_kernel<T, VEC, 1, true>), grid, block, smem, st, p, nch, rg);
-    else hipLaunchKernelGGL((combine_bwd_kernel<T, VEC, 1, false>), grid, block, smem, st, p, nch, rg);
+    if constexpr (TPOK) if (tp) hipLaunchKernelGGL((combine_bwd_kernel<T, VEC, 1, true>), grid, block, smem, st, p, nch, rg);
+    if (!tp) hipLaunchKernelGGL((combine_bwd_kernel<T, VEC, 1, false>), grid, block, smem, st, p, nch, rg);
   }
   FV_LAUNCH_CHECK();
   return FV_OK;
 }
 
 template <typename T, int VEC>
-int launch_conv_pool_bwd(const BwdParams& p, hipStream_t st) {
-  const int nch = fv_cdiv(p.d_in, 64 * VEC);
-  FV_CHECK(nch <= (VEC == 1 ? 16 : 12), "mixer_conv_pool_bwd: d_inner %d too large for the VEC=%d row walker", p.d_in, VEC);
-  const int rg = rg_convpool(p.d_in, VEC);
-  dim3 grid(conv_pool_bwd_blocks((long)p.B * p.geo.rows, p.d_in, p.geo.tpp)), block(64 * nch * rg);
-  size_t smem = (size_t)12 * p.d_in * 4;
-  FV_CHECK(smem <= 160 * 1024, "mixer_conv_pool_bwd: d_inner %d too large", p.d_in);
+int launch_conv_pool_bwd(const BwdParams& p, const fvplan::Plan& pl, hipStream_t st) {
+  const int nch = pl.waves, rg = pl.row_groups;
+  dim3 grid(conv_pool_bwd_blocks((long)p.B * p.geo.rows, p.d_in, p.geo.tpp), pl.slabs), block(64 * nch * rg);
+  const size_t smem = pl.lds_bytes;
   if (smem > 64 * 1024) {     // opt in to > 64 KiB of dynamic LDS (once per instantiation; not a stream operation)
     static FvOncePerDevice done;   
     if (done.first()) {
@@ -584,12 +586,6 @@ int launch_conv_pool_bwd(const BwdParams& p, hipStream_t st) {
       (void)hipFuncSetAttribute((const void*)conv_pool_bwd_kernel<T, VEC, 8, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       (void)0;     
     }
-  }
-  // short rows: the whole-row kernel (convpool_bwd_row.hip) over the same persistent grid / partial layout
-  static const bool rowk = (fv_tune("FASTVIM_BWD_ROWK", 1) != 0);   // tuning hook
-  if (rowk && VEC == 2 && !p.amax) {
-    int rc = fvi::conv_pool_bwd_row(p, nch, rg, (int)grid.x, smem, sizeof(T) == 4 ? FV_F32 : FV_BF16, st);
-    if (rc != FV_ERR_UNSUPPORTED) return rc;
   }
   FV_CHECK(!p.dxc2, "mixer_conv_pool_bwd2: a second pooled-gradient addend is taken by the whole-row kernel only "
                     "(mean pooling, tokens_per_patch 1, 14 or 16 columns, d_inner a multiple of 128)");
@@ -616,19 +612,26 @@ int launch_conv_pool_bwd(const BwdParams& p, hipStream_t st) {
 
 template <typename T>
 int dispatch_bwd(int which, const BwdParams& p, hipStream_t st) {
+  const int dtype = sizeof(T) == 4 ? FV_F32 : FV_BF16;
+  const fvplan::Shape sh{p.B, p.geo.rows, p.geo.pcols, p.geo.tpp, p.d_in, p.amax != nullptr, dtype};
   if (which == 0) {
-    {
-      int rc = fvi::combine_bwd_wave(p, sizeof(T) == 4 ? FV_F32 : FV_BF16, st);
-      if (rc != FV_ERR_UNSUPPORTED) return rc;
-    }
-    const int v = vec_combine(p.d_in, p.geo.tpp);
-    if (v == 6) return launch_combine_bwd<T, 6>(p, st);
-    if (v == 4) return launch_combine_bwd<T, 4>(p, st);
-    if (v == 2) return launch_combine_bwd<T, 2>(p, st);
-    return launch_combine_bwd<T, 1>(p, st);
+    const fvplan::Plan pl = fvplan::combine_bwd(sh);
+    FV_CHECK(pl.form != fvplan::UNSUPPORTED, "mixer_combine_bwd: no launch form for d_inner %d, tokens_per_patch %d (fv_mixer_plan)",
+             p.d_in, p.geo.tpp);
+    if (pl.form == fvplan::WAVE) return fvi::combine_bwd_wave(p, dtype, st);
+    if (pl.vec == 8) return launch_combine_bwd<T, 8, false>(p, pl, st);
+    if (pl.vec == 6) return launch_combine_bwd<T, 6>(p, pl, st);
+    if (pl.vec == 4) return launch_combine_bwd<T, 4>(p, pl, st);
+    if (pl.vec == 2) return launch_combine_bwd<T, 2>(p, pl, st);
+    return launch_combine_bwd<T, 1>(p, pl, st);
   }
-  if (vec_convpool(p.d_in) == 2) return launch_conv_pool_bwd<T, 2>(p, st);
-  return launch_conv_pool_bwd<T, 1>(p, st);
+  const fvplan::Plan pl = fvplan::conv_pool_bwd(sh);
+  FV_CHECK(pl.form != fvplan::UNSUPPORTED, "mixer_conv_pool_bwd: no launch form for d_inner %d (fv_mixer_plan)", p.d_in);
+  // short rows / cells: the packed-math kernels (convpool_bwd_row.hip) over the same persistent grid / partial layout
+  if (pl.form == fvplan::ROW || pl.form == fvplan::CELL)
+    return fvi::conv_pool_bwd_row(p, pl, conv_pool_bwd_blocks((long)p.B * p.geo.rows, p.d_in, p.geo.tpp), dtype, st);
+  if (pl.vec == 2) return launch_conv_pool_bwd<T, 2>(p, pl, st);
+  return launch_conv_pool_bwd<T, 1>(p, pl, st);
 }
 
 int check_geo_b(int B, int rows, int cols, int s_i, int s_j, int d_in, int dtype) {
@@ -647,8 +650,18 @@ extern "C" int fv_mixer_bwd_blocks(int batch, int rows, int d_inner, int tokens_
     const int wb = fvi::combine_wave_blocks(batch, rows, tokens_per_patch, d_inner);
     if (wb) return wb;
   }
-  return which == 0 ? persistent_blocks(n, rg_combine(d_inner, vec_combine(d_inner, tokens_per_patch)))
+  return which == 0 ? persistent_blocks(n, fvplan::combine_rg(d_inner, fvplan::combine_bwd_vec(d_inner, tokens_per_patch)))
                     : conv_pool_bwd_blocks(n, d_inner, tokens_per_patch);
+}
+
+extern "C" int fv_mixer_plan(int family, int batch, int rows, int cols, int tokens_per_patch, int d_inner, int pool_max,
+                             int dtype, int* plan) {
+  FV_CHECK(plan && family >= 0 && family <= 3 && batch > 0 && rows > 0 && cols > 0 && tokens_per_patch > 0 && d_inner > 0,
+           "mixer_plan: bad arguments");
+  const fvplan::Plan pl = fvplan::plan(family, fvplan::Shape{batch, rows, cols, tokens_per_patch, d_inner, pool_max != 0, dtype});
+  plan[0] = pl.form; plan[1] = pl.vec; plan[2] = pl.waves; plan[3] = pl.slabs; plan[4] = pl.row_groups;
+  plan[5] = pl.lds_bytes; plan[6] = pl.dxc2; plan[7] = 0;
+  return FV_OK;
 }
 
 extern "C" int fv_mixer_combine_bwd(const void* dg, const void* xz, const void* skip, const float* yc,
@@ -685,7 +698,9 @@ extern "C" int fv_mixer_conv_pool_bwd(const void* xz, const void* d_o, const flo
 }
 
 extern "C" int fv_mixer_conv_pool_bwd2_ok(int rows, int cols, int tokens_per_patch, int d_inner, int pool_max) {
-  return !pool_max && tokens_per_patch == 1 && (cols == 14 || cols == 16) && rows > 0 && d_inner % 128 == 0 && d_inner <= 2048;
+  if (rows <= 0 || cols <= 0 || tokens_per_patch <= 0 || d_inner <= 0) return 0;
+  // the dispatcher's own choice (one batch element; the storage dtype moves the block shape, not the form)
+  return fvplan::conv_pool_bwd(fvplan::Shape{1, rows, cols, tokens_per_patch, d_inner, pool_max != 0, FV_BF16}).dxc2;
 }
 
 extern "C" int fv_mixer_conv_pool_bwd2(const void* xz, const void* d_o, const float* dxc, const void* dxc2,

@@ -1,6 +1,7 @@
 // Pieces shared by the forward and backward fused-mixer kernels.
 #pragma once
 #include "rowwalk.h"
+#include "mixer_plan.h"
 
 namespace fvi {   // shared between the mixer translation units
 
@@ -34,16 +35,16 @@ struct FwdParams {
   int use_norm;
 };
 
-// Whole-row conv+pool(+skip) forward (convpool_fwd_row.hip); FV_ERR_UNSUPPORTED -> caller runs the generic kernel.
-int conv_pool_fwd_row(const FwdParams& p, int pool_max, int dtype, hipStream_t st);
+// Whole-row / cell-walking conv+pool(+skip) forward (convpool_fwd_row.hip) for a ROW or CELL plan (mixer_plan.h).
+int conv_pool_fwd_row(const FwdParams& p, const fvplan::Plan& pl, int pool_max, int dtype, hipStream_t st);
 
 constexpr int RGMAX = 4;   // a block walks up to RGMAX pooling rows concurrently (one per row group) and emits ONE partial
 
-// Whole-row conv+pool backward (convpool_bwd_row.hip).  Same grid / partial layout as the generic kernel;
-// returns FV_ERR_UNSUPPORTED when the shape is not one it is built for (the caller then runs the generic one).
-int conv_pool_bwd_row(const BwdParams& p, int nch, int rg, int grid, size_t smem, int dtype, hipStream_t st);
+// Whole-row / cell-walking conv+pool backward (convpool_bwd_row.hip) for a ROW or CELL plan (mixer_plan.h).  Same
+// persistent grid / partial layout as the generic kernel.
+int conv_pool_bwd_row(const BwdParams& p, const fvplan::Plan& pl, int grid, int dtype, hipStream_t st);
 
-// Wave-per-token combine kernels (combine_wave.hip); FV_ERR_UNSUPPORTED -> caller runs the generic kernel.
+// Wave-per-token combine kernels (combine_wave.hip) for a WAVE plan (mixer_plan.h).
 // combine_wave_blocks: grid (= rows of dLN partials) of the backward, 0 when the wave kernels do not apply.
 int combine_wave_blocks(int B, int rows, int tpp, int d_in);
 int combine_fwd_wave(const FwdParams& p, int dtype, hipStream_t st);

@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "mixer_common.h"
+#include "mixer_plan.h"
 
 namespace {
 
@@ -46,7 +47,7 @@ template <typename T, int VEC, int TJ, bool TP, bool PMAX>
 __global__ __launch_bounds__(VEC == 1 ? 1024 : 512) void conv_pool_fwd_kernel(FwdParams p) {
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int i = blockIdx.x, b = blockIdx.y;
-  const int c0 = (wv * 64 + lane) * VEC;
+  const int c0 = ((blockIdx.z * (blockDim.x >> 6) + wv) * 64 + lane) * VEC;     // channel slabs over blockIdx.z
   const bool act = c0 < p.d_in;
   const Geo g = p.geo;
   ChanParams<VEC> cp;
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(VEC == 1 ? 1024 : 512) void conv_pool_fwd_kernel(Fw
 constexpr int RGMAXF = 4;
 
 template <typename T, int VEC, int TT, bool TP>
-__global__ __launch_bounds__(VEC == 1 ? 1024 : 512) void combine_fwd_kernel(FwdParams p, int nch, int RG) {
+__global__ __launch_bounds__(VEC == 1 ? 1024 : VEC == 8 ? 320 : 512) void combine_fwd_kernel(FwdParams p, int nch, int RG) {
   __shared__ float s_red[RGMAXF * TT * 16];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -332,13 +333,10 @@ int persistent_blocks_f(long nrows, int rg) {
 }
 
 template <typename T, int VEC>
-int launch_conv_pool(const FwdParams& p, int pool_max, hipStream_t st) {
-  const int nch = fv_cdiv(p.d_in, 64 * VEC);
-  FV_CHECK(nch <= (VEC == 1 ? 16 : 8), "mixer: d_inner %d too large for the VEC=%d row-walker", p.d_in, VEC);
-  dim3 grid(p.geo.rows, p.B), block(64 * nch);
+int launch_conv_pool(const FwdParams& p, const fvplan::Plan& pl, int pool_max, hipStream_t st) {
+  dim3 grid(p.geo.rows, p.B, pl.slabs), block(64 * pl.waves);
   const bool tp = p.geo.tpp > 1;
-  const size_t smem = (tp && p.geo.pcols > 1) ? (size_t)(pool_max ? 4 : 2) * p.geo.tpp * 64 * nch * VEC * 4 : 0;
-  FV_CHECK(smem <= 160 * 1024, "mixer_conv_pool_fwd: tokens_per_patch %d too large", p.geo.tpp);
+  const size_t smem = pl.lds_bytes;
   if (smem > 64 * 1024) {     // opt in to > 64 KiB of dynamic LDS (once per instantiation; not a stream operation)
     static FvOncePerDevice done;   
     if (done.first()) {
@@ -352,11 +350,6 @@ int launch_conv_pool(const FwdParams& p, int pool_max, hipStream_t st) {
     if (pool_max) hipLaunchKernelGGL((K<__VA_ARGS__, true>), grid, block, smem, st, p);      \
     else hipLaunchKernelGGL((K<__VA_ARGS__, false>), grid, block, smem, st, p);              \
   } while (0)
-  static const bool rowk = (fv_tune("FASTVIM_FWD_ROWK", 1) != 0);   // tuning hook
-  if (rowk && !pool_max) {     // short rows / 8-token cells, mean pooling: the packed-math kernels (convpool_fwd_row.hip): the whole-row packed-math kernel (convpool_fwd_row.hip)
-    int rc = fvi::conv_pool_fwd_row(p, pool_max, sizeof(T) == 4 ? FV_F32 : FV_BF16, st);
-    if (rc != FV_ERR_UNSUPPORTED) return rc;
-  }
   if (tp) FV_CP(conv_pool_fwd_kernel, T, VEC, 8, true);
   else if (p.geo.cols % 7 == 0) FV_CP(conv_pool_fwd_kernel, T, VEC, 7, false);
   else FV_CP(conv_pool_fwd_kernel, T, VEC, 8, false);
@@ -365,14 +358,9 @@ int launch_conv_pool(const FwdParams& p, int pool_max, hipStream_t st) {
   return FV_OK;
 }
 
-int rg_combine_f(int d_in, int VEC) { int nch = fv_cdiv(d_in, 64 * VEC); int r = 8 / nch; return r < 1 ? 1 : (r > RGMAXF ? RGMAXF : r); }
-int vec_combine_f(int d_in) { return (d_in % 384 == 0 && d_in <= 8 * 384) ? 6 : (d_in % 256 == 0 && d_in <= 8 * 256) ? 4 : (d_in % 128 == 0 && d_in <= 8 * 128) ? 2 : 1; }
-
 template <typename T, int VEC>
-int launch_combine(const FwdParams& p, hipStream_t st) {
-  const int nch = fv_cdiv(p.d_in, 64 * VEC);
-  FV_CHECK(nch <= (VEC == 1 ? 16 : 8), "mixer: d_inner %d too large for the VEC=%d row-walker", p.d_in, VEC);
-  const int rg = rg_combine_f(p.d_in, VEC);
+int launch_combine(const FwdParams& p, const fvplan::Plan& pl, hipStream_t st) {
+  const int nch = pl.waves, rg = pl.row_groups;
   dim3 grid(persistent_blocks_f((long)p.B * p.geo.rows, rg)), block(64 * nch * rg);
   const bool tp = p.geo.tpp > 1;
   if (p.geo.cols % 2 == 0) {
@@ -386,26 +374,39 @@ int launch_combine(const FwdParams& p, hipStream_t st) {
   return FV_OK;
 }
 
+// 8 channels per lane (d_inner 2560 = 5 waves x 64 x 8): tokens_per_patch 1 only (fvplan::combine_wide8)
+template <typename T>
+int launch_combine8(const FwdParams& p, const fvplan::Plan& pl, hipStream_t st) {
+  const int nch = pl.waves, rg = pl.row_groups;
+  dim3 grid(persistent_blocks_f((long)p.B * p.geo.rows, rg)), block(64 * nch * rg);
+  if (p.geo.cols % 2 == 0) hipLaunchKernelGGL((combine_fwd_kernel<T, 8, 2, false>), grid, block, 0, st, p, nch, rg);
+  else hipLaunchKernelGGL((combine_fwd_kernel<T, 8, 1, false>), grid, block, 0, st, p, nch, rg);
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
 template <typename T>
 int dispatch_fwd(int which, const FwdParams& p, int pool_max, hipStream_t st) {
+  const int dtype = sizeof(T) == 4 ? FV_F32 : FV_BF16;
+  const fvplan::Shape sh{p.B, p.geo.rows, p.geo.pcols, p.geo.tpp, p.d_in, pool_max, dtype};
   if (which == 1) {
-    {
-      int rc = fvi::combine_fwd_wave(p, sizeof(T) == 4 ? FV_F32 : FV_BF16, st);
-      if (rc != FV_ERR_UNSUPPORTED) return rc;
-    }
-    const int v = vec_combine_f(p.d_in);
-    if (v == 6) return launch_combine<T, 6>(p, st);
-    if (v == 4) return launch_combine<T, 4>(p, st);
-    if (v == 2) return launch_combine<T, 2>(p, st);
-    return launch_combine<T, 1>(p, st);
+    const fvplan::Plan pl = fvplan::combine_fwd(sh);
+    FV_CHECK(pl.form != fvplan::UNSUPPORTED, "mixer_combine_fwd: no launch form for d_inner %d (fv_mixer_plan)", p.d_in);
+    if (pl.form == fvplan::WAVE) return fvi::combine_fwd_wave(p, dtype, st);
+    if (pl.vec == 8) return launch_combine8<T>(p, pl, st);
+    if (pl.vec == 6) return launch_combine<T, 6>(p, pl, st);
+    if (pl.vec == 4) return launch_combine<T, 4>(p, pl, st);
+    if (pl.vec == 2) return launch_combine<T, 2>(p, pl, st);
+    return launch_combine<T, 1>(p, pl, st);
   }
-  static const int force = fv_tune("FASTVIM_FWD_VEC", 0);   // tuning hook
-  if ((force == 2 || p.geo.tpp > 1) && p.d_in % 128 == 0 && p.d_in <= 8 * 128) return launch_conv_pool<T, 2>(p, pool_max, st);
-  if (p.geo.tpp > 1 && p.d_in % 256 == 0 && p.d_in <= 8 * 256) return launch_conv_pool<T, 4>(p, pool_max, st);
-  if (p.geo.tpp > 1) return launch_conv_pool<T, 1>(p, pool_max, st);
-  if (p.d_in % 384 == 0) return launch_conv_pool<T, 6>(p, pool_max, st);
-  if (p.d_in % 256 == 0) return launch_conv_pool<T, 4>(p, pool_max, st);
-  return launch_conv_pool<T, 1>(p, pool_max, st);
+  const fvplan::Plan pl = fvplan::conv_pool_fwd(sh);
+  FV_CHECK(pl.form != fvplan::UNSUPPORTED, "mixer_conv_pool_fwd: no launch form for d_inner %d, tokens_per_patch %d (fv_mixer_plan)",
+           p.d_in, p.geo.tpp);
+  if (pl.form == fvplan::ROW || pl.form == fvplan::CELL) return fvi::conv_pool_fwd_row(p, pl, pool_max, dtype, st);
+  if (pl.vec == 6) return launch_conv_pool<T, 6>(p, pl, pool_max, st);
+  if (pl.vec == 4) return launch_conv_pool<T, 4>(p, pl, pool_max, st);
+  if (pl.vec == 2) return launch_conv_pool<T, 2>(p, pl, pool_max, st);
+  return launch_conv_pool<T, 1>(p, pl, pool_max, st);
 }
 
 int check_geo(int B, int rows, int cols, int s_i, int s_j, int d_in, int dtype, int tpp) {

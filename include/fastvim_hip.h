@@ -50,7 +50,11 @@ const char* fv_last_error(void);
  *      Later, still 3: fv_mix_batch, fv_patch_unfold_mix, fv_mixup_target and fv_label_ce were ADDED (batch Mixup /
  *      CutMix and the losses on integer labels).
  *      Later, still 3: fv_patch_unfold_chan, fv_chan_embed_table and fv_chan_embed_scatter were ADDED (hierarchical
- *      channel sampling of the channel models with the drawn subset in device memory). */
+ *      channel sampling of the channel models with the drawn subset in device memory).
+ *      Later, still 3: fv_mixer_plan was ADDED (the launch plan of the mixer's row kernels, which now serve d_inner
+ *      2048 and 2560: FastVim-L / -H).  fv_mixer_conv_pool_bwd2_ok is defined from it and therefore answers no
+ *      for 1536 < d_inner <= 2048 that is not a multiple of 256 -- widths whose launch always failed -- and yes
+ *      for the multiples of 256 up to 3072; no signature changed, so the number stays. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -200,6 +204,20 @@ int fv_mixer_combine_fwd(const void* xz, const void* skip, const float* yc, cons
  * Number of persistent blocks a row-walking backward kernel launches (which = 0: combine_bwd,
  * 1: conv_pool_bwd); their `partials` buffers are (blocks, 2*d_inner) and (blocks, 12*d_inner) fp32. */
 int fv_mixer_bwd_blocks(int batch, int rows, int d_inner, int tokens_per_patch, int which);
+
+/* Launch plan of one of the mixer's four row-kernel families for a shape -- what the launchers themselves ask before
+ * they launch (host code only, no HIP call: usable without a GPU).
+ *   family: 0 fv_mixer_conv_pool_fwd, 1 fv_mixer_combine_fwd, 2 fv_mixer_combine_bwd, 3 fv_mixer_conv_pool_bwd(2)
+ *   cols  : patch columns of a pooling row;  pool_max, dtype as in the launch
+ *   plan[8] <- { form, vec, waves, slabs, row_groups, lds_bytes, takes_dxc2, 0 }
+ *     form       0 unsupported (the launch returns an error), 1 generic tile / streaming kernel, 2 whole-row kernel
+ *                (14 / 16 columns), 3 cell walker (tokens_per_patch 8, long dense rows), 4 wave-per-token kernel
+ *     vec        channels per lane;  waves: channel waves of a block per row group;  slabs: blocks that cover d_inner
+ *                (slabs * waves * 64 * vec == d_inner for a multiple of 64);  row_groups: pooling rows a block walks at
+ *                a time (waves * row_groups * 64 threads);  lds_bytes: LDS of a block
+ *     takes_dxc2 family 3: the form takes the second pooled-gradient addend of fv_mixer_conv_pool_bwd2 */
+int fv_mixer_plan(int family, int batch, int rows, int cols, int tokens_per_patch, int d_inner, int pool_max, int dtype,
+                  int* plan);
 
 /* Adjoint of the LayerNorm + gate of fv_mixer_combine_fwd; the normalised value is rebuilt from the saved
  * skip, yc, mean, rstd.  dg: gradient wrt g.
