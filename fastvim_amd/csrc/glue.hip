@@ -257,6 +257,111 @@ __global__ __launch_bounds__(1024) void patch_unfold_mix_kernel(const TI* __rest
   }
 }
 
+// ---- patch unfold, any even patch width from 8 up (patch 14: FastVim-H, MAE-H) ----------------------------------------
+// The kernels above need pw % 8 == 0: a 4-element vector of an image row stays inside one patch and every patch row is a
+// 16-byte multiple.  With pw = 14 a 4-element vector straddles a patch boundary every other time (14 % 4 = 2), so it is
+// placed into the tile as two 2-element halves (pw even: a pair never straddles).  LV = 4 needs W % 4 == 0 (every image
+// row and every chunk's segment then start and end on whole vectors); LV = 2 serves any even W.  The chunk of patches is
+// still one contiguous stretch of `out`, but it starts on a 16-byte boundary only for some grids (588 bf16 elements per
+// patch are 8-byte multiples; 16 patches are 16-byte ones): `sw`, the bytes per tile store (16, 8 or 4), is the host's
+// choice from the actual chunk starts and lengths.
+template <typename T> struct Vec2;      // two consecutive elements <-> two floats
+template <> struct Vec2<float> {
+  static __device__ __forceinline__ void ld(const float* p, float (&v)[2]) {
+    const float2 t = *reinterpret_cast<const float2*>(p);
+    v[0] = t.x; v[1] = t.y;
+  }
+  static __device__ __forceinline__ void st(float* p, float a, float b) { *reinterpret_cast<float2*>(p) = make_float2(a, b); }
+};
+template <> struct Vec2<bf16_t> {
+  static __device__ __forceinline__ void ld(const bf16_t* p, float (&v)[2]) {
+    const uint32_t t = *reinterpret_cast<const uint32_t*>(p);
+    v[0] = __uint_as_float(t << 16); v[1] = __uint_as_float(t & 0xffff0000u);
+  }
+  static __device__ __forceinline__ void st(bf16_t* p, float a, float b) { *reinterpret_cast<uint32_t*>(p) = pack_bf16x2(a, b); }
+};
+template <typename T, int LV> __device__ __forceinline__ void ld_row(const T* p, float (&v)[LV]) {
+  if constexpr (LV == 4) Vec4<T>::ld(p, v); else Vec2<T>::ld(p, v);
+}
+
+// LV elements of row `row` (= c * ph + pi) at column x of the chunk's image-row segment -> their patches' tile rows
+template <typename TO, int LV>
+__device__ __forceinline__ void place_pairs(TO* tile, int Kp, int pw, int row, int x, const float (&v)[LV]) {
+#pragma unroll
+  for (int h = 0; h < LV; h += 2) {
+    const int gj = (x + h) / pw, pj = (x + h) - gj * pw;
+    Vec2<TO>::st(tile + (size_t)gj * Kp + row * pw + pj, v[h], v[h + 1]);
+  }
+}
+
+// n elements (a multiple of sw bytes, dst sw-byte aligned) from the tile to `out`
+template <typename TO>
+__device__ __forceinline__ void drain_tile(TO* dst, const TO* tile, int n, int sw) {
+  const int nb = n * (int)sizeof(TO);
+  if (sw == 16) {
+    for (int e = threadIdx.x; e < nb / 16; e += blockDim.x) reinterpret_cast<u32x4*>(dst)[e] = reinterpret_cast<const u32x4*>(tile)[e];
+  } else if (sw == 8) {
+    for (int e = threadIdx.x; e < nb / 8; e += blockDim.x) reinterpret_cast<u32x2*>(dst)[e] = reinterpret_cast<const u32x2*>(tile)[e];
+  } else {
+    for (int e = threadIdx.x; e < nb / 4; e += blockDim.x) reinterpret_cast<uint32_t*>(dst)[e] = reinterpret_cast<const uint32_t*>(tile)[e];
+  }
+}
+
+template <typename TI, typename TO, int LV>
+__global__ __launch_bounds__(256) void patch_unfold_even_kernel(const TI* __restrict__ img, TO* __restrict__ out, int C, int H,
+                                                                int W, int ph, int pw, int gw, int sw) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  TO* tile = reinterpret_cast<TO*>(smem);
+  const int gj0 = blockIdx.x * UNF_GJ, gi = blockIdx.y, b = blockIdx.z;
+  const int gjn = min(UNF_GJ, gw - gj0);
+  const int Kp = C * ph * pw;                 // elements per patch row
+  const int xv = gjn * pw / LV;               // LV-element vectors per image-row segment of the chunk
+  const TI* src = img + ((size_t)b * C * H + (size_t)gi * ph) * W + (size_t)gj0 * pw;
+  for (int e = threadIdx.x; e < C * ph * xv; e += blockDim.x) {
+    const int row = e / xv, x = (e - row * xv) * LV;     // row = c * ph + pi
+    const int c = row / ph, pi = row - c * ph;
+    float v[LV];
+    ld_row<TI, LV>(src + ((size_t)c * H + pi) * W + x, v);
+    place_pairs<TO, LV>(tile, Kp, pw, row, x, v);
+  }
+  __syncthreads();
+  drain_tile<TO>(out + (((size_t)b * gridDim.y + gi) * gw + gj0) * Kp, tile, gjn * Kp, sw);
+}
+
+// patch_unfold_mix_kernel for any even patch width: the same mixing expressions on the same operands, LV pixels at a time
+template <typename TI, typename TO, int LV>
+__global__ __launch_bounds__(1024) void patch_unfold_mix_even_kernel(const TI* __restrict__ img, TO* __restrict__ out,
+                                                                    const fv_mix_params* __restrict__ mp, int B, int C, int H,
+                                                                    int W, int ph, int pw, int gw, int gjc, int sw) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const fv_mix_params P = *mp;
+  const int mode = mix_mode(P);
+  const int gj0 = blockIdx.x * gjc, gi = blockIdx.y, ba = blockIdx.z, bp = B - 1 - ba;
+  const int gjn = min(gjc, gw - gj0);
+  const int Kp = C * ph * pw;                 // elements per patch row
+  const int xv = gjn * pw / LV;               // LV-element vectors per image-row segment of the chunk
+  TO* tile_a = reinterpret_cast<TO*>(smem);
+  TO* tile_p = tile_a + (size_t)gjc * Kp;
+  const size_t org = (size_t)gi * ph * W + (size_t)gj0 * pw;
+  const TI* src_a = img + (size_t)ba * C * H * W + org;
+  const TI* src_p = img + (size_t)bp * C * H * W + org;
+  for (int e = threadIdx.x; e < C * ph * xv; e += blockDim.x) {
+    const int row = e / xv, x = (e - row * xv) * LV;     // row = c * ph + pi
+    const int c = row / ph, pi = row - c * ph;
+    const size_t off = ((size_t)c * H + pi) * W + x;
+    float a[LV], p[LV], ra[LV], rp[LV];
+    ld_row<TI, LV>(src_a + off, a);
+    ld_row<TI, LV>(src_p + off, p);
+    mix_pixels<TI, LV>(P, mode, gi * ph + pi, gj0 * pw + x, a, p, ra, rp);
+    place_pairs<TO, LV>(tile_a, Kp, pw, row, x, ra);
+    place_pairs<TO, LV>(tile_p, Kp, pw, row, x, rp);
+  }
+  __syncthreads();
+  const size_t chunk = ((size_t)gi * gw + gj0) * Kp, image = (size_t)gridDim.y * gw * Kp;
+  drain_tile<TO>(out + (size_t)ba * image + chunk, tile_a, gjn * Kp, sw);
+  drain_tile<TO>(out + (size_t)bp * image + chunk, tile_p, gjn * Kp, sw);
+}
+
 // ---- token mean pool: out[b][d] = (1/L) sum_l x[b][l][d] ------------------------------------------------------------
 // One 16-wave workgroup per (batch element, 4*64-channel slab): lane = 4 channels, the waves split the tokens (four
 // loads in flight each -- with 4 waves and one load in flight the 196-token sum was 49 dependent round trips, 15 us),
@@ -404,6 +509,16 @@ __global__ __launch_bounds__(256) void pack_weight_frags_kernel(PackJobs J) {
   J.dst[blockIdx.y][u] = J.src[blockIdx.y][row * (J.ks_n * 4) + unit_in_row];
 }
 
+// Bytes per tile store of the even-width unfold forms.  Chunks of `gjc` patches start at patch (b*gh + gi)*gw + k*gjc and
+// hold gjc or gw - k*gjc patches: every start and length is a multiple of gcd(gw, gjc) patches of `patch_bytes` each
+// (a multiple of 4: the width is even, an element at least 2 bytes), and `out` itself is 16-byte aligned.
+int unfold_store_bytes(int gw, int gjc, size_t patch_bytes) {
+  int a = gw, b = gjc;
+  while (b) { const int t = a % b; a = b; b = t; }
+  const size_t unit = (size_t)a * patch_bytes;
+  return unit % 16 == 0 ? 16 : unit % 8 == 0 ? 8 : 4;
+}
+
 }  // namespace
 
 extern "C" int fv_patch_unfold(const void* img, int img_dtype, void* out, int out_dtype, int batch, int chans, int height,
@@ -412,8 +527,8 @@ extern "C" int fv_patch_unfold(const void* img, int img_dtype, void* out, int ou
   FV_CHECK(dt_ok(img_dtype) && dt_ok(out_dtype), "patch_unfold: dtypes must be fp32 or bf16");
   FV_CHECK(batch > 0 && chans > 0 && ph > 0 && pw > 0 && height >= ph && width >= pw, "patch_unfold: empty dimension");
   FV_CHECK(height % ph == 0 && width % pw == 0, "patch_unfold: image %dx%d is not whole %dx%d patches", height, width, ph, pw);
-  FV_CHECK(pw % 8 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)out & 15) == 0,
-           "patch_unfold: patch width must be a multiple of 8 and the buffers 16-byte aligned");
+  FV_CHECK(pw % 2 == 0 && pw >= 8 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)out & 15) == 0,
+           "patch_unfold: patch width must be even and at least 8, and the buffers 16-byte aligned");
   const int gh = height / ph, gw = width / pw;
   const size_t osz = out_dtype == FV_F32 ? 4 : 2;
   const size_t smem = (size_t)UNF_GJ * chans * ph * pw * osz;
@@ -421,6 +536,18 @@ extern "C" int fv_patch_unfold(const void* img, int img_dtype, void* out, int ou
   FV_CHECK(gh <= 65535 && batch <= 65535, "patch_unfold: grid too large");
   const dim3 grid(fv_cdiv(gw, UNF_GJ), gh, batch), block(256);
   hipStream_t st = (hipStream_t)stream;
+  if (pw % 8 != 0) {
+    const int sw = unfold_store_bytes(gw, UNF_GJ, (size_t)chans * ph * pw * osz);
+#define FV_UNFE(TI, TO) do { if (width % 4 == 0) hipLaunchKernelGGL((patch_unfold_even_kernel<TI, TO, 4>), grid, block, smem, st, (const TI*)img, (TO*)out, chans, height, width, ph, pw, gw, sw); \
+                             else hipLaunchKernelGGL((patch_unfold_even_kernel<TI, TO, 2>), grid, block, smem, st, (const TI*)img, (TO*)out, chans, height, width, ph, pw, gw, sw); } while (0)
+    if (img_dtype == FV_F32 && out_dtype == FV_BF16) FV_UNFE(float, bf16_t);
+    else if (img_dtype == FV_F32) FV_UNFE(float, float);
+    else if (out_dtype == FV_BF16) FV_UNFE(bf16_t, bf16_t);
+    else FV_UNFE(bf16_t, float);
+#undef FV_UNFE
+    FV_LAUNCH_CHECK();
+    return FV_OK;
+  }
 #define FV_UNF(TI, TO) hipLaunchKernelGGL((patch_unfold_kernel<TI, TO>), grid, block, smem, st, (const TI*)img, (TO*)out, chans, height, width, ph, pw, gw)
   if (img_dtype == FV_F32 && out_dtype == FV_BF16) FV_UNF(float, bf16_t);
   else if (img_dtype == FV_F32) FV_UNF(float, float);
@@ -519,8 +646,8 @@ extern "C" int fv_patch_unfold_mix(const void* img, int img_dtype, void* out, in
   FV_CHECK(batch > 0 && chans > 0 && ph > 0 && pw > 0 && height >= ph && width >= pw, "patch_unfold_mix: empty dimension");
   FV_CHECK(batch % 2 == 0, "patch_unfold_mix: batch mode pairs image b with image batch-1-b, the batch (%d) must be even", batch);
   FV_CHECK(height % ph == 0 && width % pw == 0, "patch_unfold_mix: image %dx%d is not whole %dx%d patches", height, width, ph, pw);
-  FV_CHECK(pw % 8 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)out & 15) == 0,
-           "patch_unfold_mix: patch width must be a multiple of 8 and the buffers 16-byte aligned");
+  FV_CHECK(pw % 2 == 0 && pw >= 8 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)out & 15) == 0,
+           "patch_unfold_mix: patch width must be even and at least 8, and the buffers 16-byte aligned");
   const int gh = height / ph, gw = width / pw;
   const size_t osz = out_dtype == FV_F32 ? 4 : 2;
   // Two tiles per workgroup.  What this kernel is short of is loads in flight per byte of LDS: with fv_patch_unfold's
@@ -537,6 +664,19 @@ extern "C" int fv_patch_unfold_mix(const void* img, int img_dtype, void* out, in
   const dim3 grid(fv_cdiv(gw, gjc), gh, batch / 2), block(threads);
   hipStream_t st = (hipStream_t)stream;
   const fv_mix_params* mp = (const fv_mix_params*)mix;
+  if (pw % 8 != 0) {
+    FV_CHECK(gjc % 2 == 0, "patch_unfold_mix: patch width %d needs an even number of patches per tile (got %d)", pw, gjc);
+    const int sw = unfold_store_bytes(gw, gjc, (size_t)chans * ph * pw * osz);
+#define FV_UNFME(TI, TO) do { if (width % 4 == 0) hipLaunchKernelGGL((patch_unfold_mix_even_kernel<TI, TO, 4>), grid, block, smem, st, (const TI*)img, (TO*)out, mp, batch, chans, height, width, ph, pw, gw, gjc, sw); \
+                              else hipLaunchKernelGGL((patch_unfold_mix_even_kernel<TI, TO, 2>), grid, block, smem, st, (const TI*)img, (TO*)out, mp, batch, chans, height, width, ph, pw, gw, gjc, sw); } while (0)
+    if (img_dtype == FV_F32 && out_dtype == FV_BF16) FV_UNFME(float, bf16_t);
+    else if (img_dtype == FV_F32) FV_UNFME(float, float);
+    else if (out_dtype == FV_BF16) FV_UNFME(bf16_t, bf16_t);
+    else FV_UNFME(bf16_t, float);
+#undef FV_UNFME
+    FV_LAUNCH_CHECK();
+    return FV_OK;
+  }
 #define FV_UNFM(TI, TO) hipLaunchKernelGGL((patch_unfold_mix_kernel<TI, TO>), grid, block, smem, st, (const TI*)img, (TO*)out, mp, batch, chans, height, width, ph, pw, gw, gjc)
   if (img_dtype == FV_F32 && out_dtype == FV_BF16) FV_UNFM(float, bf16_t);
   else if (img_dtype == FV_F32) FV_UNFM(float, float);

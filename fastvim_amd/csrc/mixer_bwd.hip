@@ -619,7 +619,14 @@ int dispatch_bwd(int which, const BwdParams& p, hipStream_t st) {
     FV_CHECK(pl.form != fvplan::UNSUPPORTED, "mixer_combine_bwd: no launch form for d_inner %d, tokens_per_patch %d (fv_mixer_plan)",
              p.d_in, p.geo.tpp);
     if (pl.form == fvplan::WAVE) return fvi::combine_bwd_wave(p, dtype, st);
-    if (pl.vec == 8) return launch_combine_bwd<T, 8, false>(p, pl, st);
+    if (pl.vec == 8) {      // tokens_per_patch 1 kernels only: rows x 1 x t is the same memory as rows*t x 1 x 1, launched as that
+      BwdParams q = p;
+      if (fvplan::combine_redescribed(pl.vec, p.geo.pcols, p.geo.tpp)) {
+        FV_CHECK(p.geo.s_j == 1, "mixer_combine_bwd: d_inner %d with tokens_per_patch %d needs the natural token order", p.d_in, p.geo.tpp);
+        q.geo = make_geo(p.geo.rows * p.geo.tpp, 1, 1, 1, 1);
+      }
+      return launch_combine_bwd<T, 8, false>(q, pl, st);
+    }
     if (pl.vec == 6) return launch_combine_bwd<T, 6>(p, pl, st);
     if (pl.vec == 4) return launch_combine_bwd<T, 4>(p, pl, st);
     if (pl.vec == 2) return launch_combine_bwd<T, 2>(p, pl, st);
@@ -650,7 +657,12 @@ extern "C" int fv_mixer_bwd_blocks(int batch, int rows, int d_inner, int tokens_
     const int wb = fvi::combine_wave_blocks(batch, rows, tokens_per_patch, d_inner);
     if (wb) return wb;
   }
-  return which == 0 ? persistent_blocks(n, fvplan::combine_rg(d_inner, fvplan::combine_bwd_vec(d_inner, tokens_per_patch)))
+  // no column argument: tokens_per_patch > 1 is served at the 8-channel widths for one patch column only, as rows*tpp
+  // one-token rows (fvplan::combine_redescribed); elsewhere the row groups do not depend on the columns
+  const int vec = fvplan::combine_bwd_vec(d_inner, 1, tokens_per_patch);
+  if (which == 0 && fvplan::combine_redescribed(vec, 1, tokens_per_patch))
+    return persistent_blocks(n * tokens_per_patch, fvplan::combine_rg(d_inner, vec));
+  return which == 0 ? persistent_blocks(n, fvplan::combine_rg(d_inner, vec))
                     : conv_pool_bwd_blocks(n, d_inner, tokens_per_patch);
 }
 

@@ -374,9 +374,16 @@ int launch_combine(const FwdParams& p, const fvplan::Plan& pl, hipStream_t st) {
   return FV_OK;
 }
 
-// 8 channels per lane (d_inner 2560 = 5 waves x 64 x 8): tokens_per_patch 1 only (fvplan::combine_wide8)
+// 8 channels per lane (d_inner 2560 = 5 waves x 64 x 8): tokens_per_patch 1 kernels only (fvplan::combine_wide8); the
+// un-pooled geometry rows x 1 x t is the same memory as rows*t x 1 x 1 and is launched as that
 template <typename T>
-int launch_combine8(const FwdParams& p, const fvplan::Plan& pl, hipStream_t st) {
+int launch_combine8(const FwdParams& p_in, const fvplan::Plan& pl, hipStream_t st) {
+  FwdParams p = p_in;
+  if (fvplan::combine_redescribed(pl.vec, p.geo.pcols, p.geo.tpp)) {
+    FV_CHECK(p.geo.s_j == 1, "mixer_combine_fwd: d_inner %d with tokens_per_patch %d needs the natural token order", p.d_in, p.geo.tpp);
+    p.geo = make_geo(p.geo.rows * p.geo.tpp, 1, 1, 1, 1);
+  }
+  FV_CHECK(p.geo.tpp == 1, "mixer_combine_fwd: 8 channels per lane serve tokens_per_patch 1 or one patch column only");
   const int nch = pl.waves, rg = pl.row_groups;
   dim3 grid(persistent_blocks_f((long)p.B * p.geo.rows, rg)), block(64 * nch * rg);
   if (p.geo.cols % 2 == 0) hipLaunchKernelGGL((combine_fwd_kernel<T, 8, 2, false>), grid, block, 0, st, p, nch, rg);

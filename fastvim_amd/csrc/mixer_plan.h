@@ -136,17 +136,28 @@ inline bool combine_wave_wide_bwd(int d_in) {
 // Generic combine kernels: channels per lane.  A row of up to 8 waves x 6 / 4 / 2 channels, else one channel per lane
 // up to 16 waves -- and, past those (d_inner 2560: 40 waves of single channels), 8 channels per lane on up to 8 waves
 // (2560 = 5 waves x 64 x 8): two 16-byte accesses per lane and tensor, the row's sums still one LDS exchange.
-inline int combine_wide8(int d_in, int tpp) { return tpp == 1 && d_in > 16 * 64 && d_in % 512 == 0 && d_in <= 8 * 512; }
-inline int combine_fwd_vec(int d_in, int tpp) {
+// The 8-channel kernels are built for tokens_per_patch 1 only.  The un-pooled geometry (one patch column, every token
+// its own pooling group: the masked MAE encoders and the un-pooled Vim mixer run as rows x 1 x t) still takes them: with
+// one column, rows x 1 x t addresses exactly the memory of rows*t x 1 x 1 -- token i*t + c, yc / dyc row i*t + c -- and
+// is launched as that (combine_redescribed).  tokens_per_patch > 1 with more than one patch column (the channel
+// models' LDS slot accumulators) stays unsupported at these widths: no reference model has it.
+inline int combine_wide8(int d_in, int pcols, int tpp) {
+  return (tpp == 1 || pcols == 1) && d_in > 16 * 64 && d_in % 512 == 0 && d_in <= 8 * 512;
+}
+inline int combine_fwd_vec(int d_in, int pcols, int tpp) {
   const int v = (d_in % 384 == 0 && d_in <= 8 * 384) ? 6 : (d_in % 256 == 0 && d_in <= 8 * 256) ? 4 : (d_in % 128 == 0 && d_in <= 8 * 128) ? 2 : 1;
-  return (v == 1 && combine_wide8(d_in, tpp)) ? 8 : v;
+  return (v == 1 && combine_wide8(d_in, pcols, tpp)) ? 8 : v;
 }
-inline int combine_bwd_vec(int d_in, int tpp) {
+inline int combine_bwd_vec(int d_in, int pcols, int tpp) {
+  int v;
   if (tpp > 1)      // LDS slot accumulators: keep the per-lane state small
-    return (d_in % 128 == 0 && d_in <= 8 * 128) ? 2 : (d_in % 256 == 0 && d_in <= 8 * 256) ? 4 : 1;
-  const int v = (d_in % 384 == 0 && d_in <= 8 * 384) ? 6 : (d_in % 256 == 0 && d_in <= 8 * 256) ? 4 : 1;
-  return (v == 1 && combine_wide8(d_in, tpp)) ? 8 : v;
+    v = (d_in % 128 == 0 && d_in <= 8 * 128) ? 2 : (d_in % 256 == 0 && d_in <= 8 * 256) ? 4 : 1;
+  else
+    v = (d_in % 384 == 0 && d_in <= 8 * 384) ? 6 : (d_in % 256 == 0 && d_in <= 8 * 256) ? 4 : 1;
+  return (v == 1 && combine_wide8(d_in, pcols, tpp)) ? 8 : v;
 }
+// the launch walks rows*tpp one-token rows with the tokens_per_patch 1 kernels (natural token order only)
+inline bool combine_redescribed(int vec, int pcols, int tpp) { return vec == 8 && pcols == 1 && tpp > 1; }
 inline int combine_rg(int d_in, int vec) {
   const int nch = fv_cdiv(d_in, 64 * vec), r = 8 / nch;
   return r < 1 ? 1 : (r > RGMAX ? RGMAX : r);
@@ -158,9 +169,9 @@ inline Plan combine_fwd(const Shape& s) {
     r = Plan{WAVE, s.d_in / 64, 1, 1, WAVE_NW, 0, 0};
     return r;
   }
-  const int v = combine_fwd_vec(s.d_in, s.tpp), nch = fv_cdiv(s.d_in, 64 * v);
+  const int v = combine_fwd_vec(s.d_in, s.cols, s.tpp), nch = fv_cdiv(s.d_in, 64 * v);
   if (nch > (v == 1 ? 16 : 8)) return r;
-  const int tt = s.cols * s.tpp % 2 == 0 ? 2 : 1;
+  const int tt = (s.cols * s.tpp % 2 == 0 && !combine_redescribed(v, s.cols, s.tpp)) ? 2 : 1;
   r = Plan{GENERIC, v, nch, 1, combine_rg(s.d_in, v), RGMAX * tt * 16 * 4, 0};
   return r;
 }
@@ -171,9 +182,9 @@ inline Plan combine_bwd(const Shape& s) {
     r = Plan{WAVE, s.d_in / 64, 1, 1, WAVE_NW, 2 * s.d_in * 4, 0};
     return r;
   }
-  const int v = combine_bwd_vec(s.d_in, s.tpp), nch = fv_cdiv(s.d_in, 64 * v);
+  const int v = combine_bwd_vec(s.d_in, s.cols, s.tpp), nch = fv_cdiv(s.d_in, 64 * v);
   if (nch > (v == 1 ? 16 : 8)) return r;
-  const int rg = combine_rg(s.d_in, v), tt = s.cols * s.tpp % 2 == 0 ? 2 : 1;
+  const int rg = combine_rg(s.d_in, v), tt = (s.cols * s.tpp % 2 == 0 && !combine_redescribed(v, s.cols, s.tpp)) ? 2 : 1;
   const size_t extra = (s.tpp > 1 && s.cols > 1) ? (size_t)s.tpp * 64 * nch * rg * v : 0;
   if ((RGMAX * 64 + 2 * (size_t)s.d_in + extra) * 4 > 64 * 1024) return r;
   r = Plan{GENERIC, v, nch, 1, rg, (int)((RGMAX * 2 * tt * 16 + 2 * (size_t)s.d_in + extra) * 4), 0};

@@ -120,6 +120,7 @@ class MaskedAutoencoderViM(_FastVimMAE):
 
 
 def _mae_vim(embed_dim, depth, patch_size, stride, kwargs):
+    depth = kwargs.pop("depth", depth)      # a shallower copy of the same widths (tests, tools); the reference fixes it
     model = MaskedAutoencoderViM(patch_size=patch_size, stride=stride, embed_dim=embed_dim, depth=depth,
                                  decoder_embed_dim=512, decoder_depth=2, rms_norm=True, residual_in_fp32=True,
                                  fused_add_norm=True, **kwargs)

@@ -22,7 +22,8 @@ def patch_unfold(x, ph, pw, out_dtype):
 
 
 def patch_unfold_ok(x, ph, pw):
-    return (x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and pw % 8 == 0
+    """Any even patch width from 8 up: multiples of 8 take the 16-byte form, the others (patch 14) the 2-element-pair form."""
+    return (x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and pw % 2 == 0 and pw >= 8
             and x.shape[2] % ph == 0 and x.shape[3] % pw == 0 and x.shape[1] * ph * pw * 16 * 4 <= 64 * 1024)
 
 

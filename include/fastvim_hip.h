@@ -54,7 +54,11 @@ const char* fv_last_error(void);
  *      Later, still 3: fv_mixer_plan was ADDED (the launch plan of the mixer's row kernels, which now serve d_inner
  *      2048 and 2560: FastVim-L / -H).  fv_mixer_conv_pool_bwd2_ok is defined from it and therefore answers no
  *      for 1536 < d_inner <= 2048 that is not a multiple of 256 -- widths whose launch always failed -- and yes
- *      for the multiples of 256 up to 3072; no signature changed, so the number stays. */
+ *      for the multiples of 256 up to 3072; no signature changed, so the number stays.
+ *      Later, still 3: two preconditions were RELAXED, nothing added.  fv_patch_unfold and fv_patch_unfold_mix take any
+ *      even patch width from 8 up (was: a multiple of 8; patch 14 of FastVim-H / MAE-H), and fv_mixer_combine_fwd / _bwd serve
+ *      d_inner 2560 (and the other multiples of 512 from 1536 to 4096 that had no form) with tokens_per_patch > 1 when
+ *      there is one patch column (the un-pooled geometry of the masked MAE encoders and the Vim mixer). */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -586,7 +590,9 @@ int fv_soft_target_ce(const void* logits, int logits_dtype, const float* target,
  * ---------------------------------------------------------------------- */
 /* The k == stride patch-embed Conv2d (models/fastvim.py:95) as a GEMM: its A operand, unfolded and cast in one pass.
  *   out[b][gi*gw + gj][(c*ph + pi)*pw + pj] = img[b][c][gi*ph + pi][gj*pw + pj]
- * img (batch, chans, height, width), out (batch, gh*gw, chans*ph*pw); fp32 or bf16 each; pw % 8 == 0. */
+ * img (batch, chans, height, width), out (batch, gh*gw, chans*ph*pw); fp32 or bf16 each; pw even and at least 8 (a multiple of 8
+ * takes 16-byte accesses throughout, any other even width places 2-element pairs and stores 16, 8 or 4 bytes at a
+ * time, whichever the grid's chunk boundaries allow). */
 int fv_patch_unfold(const void* img, int img_dtype, void* out, int out_dtype, int batch, int chans, int height,
                     int width, int ph, int pw, fv_stream_t stream);
 /* fv_gemm_bf16(a_k_slow = b_k_slow = 0) with fp32 C = bf16_round(A B^T) + table[(m mod period)][n]: the patch
