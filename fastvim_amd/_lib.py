@@ -33,6 +33,7 @@ C_ABI_SYMBOLS = (
     "fv_mix_batch", "fv_patch_unfold_mix", "fv_mixup_target", "fv_label_ce",
     "fv_patch_unfold_chan", "fv_chan_embed_table", "fv_chan_embed_scatter",
     "fv_mixer_plan",
+    "fv_bn1d_stats", "fv_bn1d_apply", "fv_bn1d_bwd", "fv_sgd_flat", "fv_lars_partials_per_segment", "fv_lars_sumsq_partials", "fv_lars_flat",
 )
 
 

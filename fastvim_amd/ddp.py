@@ -23,8 +23,9 @@ opt-in (``comm_dtype=torch.bfloat16``, or ``"auto"``: bf16 for buckets whose fp3
 detection-only fp16 hook (detection/vitdet/fp16_compression_hook.py:17-26).  With it the gradient stays fp32 on both sides
 of the wire: a bucket is rounded once to bf16, summed by RCCL IN bf16 (a ring of N ranks rounds once per hop: the error
 grows with N, tests/test_ddp_cpu.py bounds N = 2 and N = 8), and written back into the fp32 buffer.
-No BatchNorm exists in FastVim, so nothing else is
-exchanged.  The same class is the whole-buffer exchange (one bucket) used by
+The backbone has no BatchNorm, so nothing else is exchanged by the training and fine-tuning steps; the linear-probe head
+does have one (``fastvim_amd.linear_probe.ProbeBatchNorm1d``, a SyncBatchNorm under the recipe's ``sync_batchnorm=True``),
+whose forward all-gathers one table row of 2 d + 1 floats per rank (``linear_probe.gather_table``).  The same class is the whole-buffer exchange (one bucket) used by
 ``FlatTrainingState.allreduce_mean_`` and by the CPU (gloo) tests.
 """
 import torch

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from .layernorm import RMSNorm, layer_norm_fn, rms_norm_fn
+from .linear_probe import is_probe_head, probe_head_forward
 from . import glue_ops as G
 from . import mamba_simple_faster as msf
 from .mamba_simple_faster import (ChainedBlockFn, LinearFn, Mamba, OutProjAddNormFn, _compute_dtype, _direct_grad, _shadow,
@@ -563,6 +564,9 @@ class VisionMamba(nn.Module):
             # F.linear(x, head.weight, head.bias) (models/fastvim.py:541) through the MFMA GEMM: at batch 128 the
             # library picks a one-workgroup kernel for this 128 x 1000 x 192 problem (25 us)
             x = LinearFn.apply(x, self.head.weight, _compute_dtype(x), self.head.bias)
+        elif is_probe_head(self.head) and x.is_cuda:
+            # the linear-probe head (mae/linear_imagenet.py:43-48): BatchNorm1d kernels, then the same GEMM
+            x = probe_head_forward(self.head, x)
         else:
             x = self.head(x)
         if self.final_pool_type == "max":

@@ -623,6 +623,116 @@ class FlatAdamW:
         f.refresh_transposed()
 
 
+def build_segment_table(names, offsets, shapes):
+    """The LARS segment table of a flat layout -- a pure function (no device): one row ``(first element, element count,
+    ndim > 1)`` per parameter, in layout order, as a CPU int64 tensor (rows, 3)."""
+    rows = []
+    for n in names:
+        shp = tuple(shapes[n])
+        k = 1
+        for s in shp:
+            k *= int(s)
+        rows.append((int(offsets[n]), k, 1 if len(shp) > 1 else 0))
+    return torch.tensor(rows, dtype=torch.int64).view(-1, 3)
+
+
+class FlatSGD:
+    """``torch.optim.SGD(momentum, weight_decay)`` (dampening 0, no Nesterov) -- or, with ``lars=True``, the reference's
+    ``LARS`` (mae/lars.py) -- over a FlatTrainingState, with the bf16 shadow refresh in the same pass (csrc/sgd_lars.hip):
+    the optimizers of the linear-probe recipe (mae/linear_imagenet.py:229-235).  ``lr`` lives in device memory
+    (``set_lr``), so a captured HIP graph replays with a changing schedule.  ``no_decay``: parameter names excluded from
+    weight decay (SGD).  LARS takes its own rule instead (lars.py:29): parameters with ``ndim <= 1`` get neither weight
+    decay nor the trust ratio ``q = trust_coefficient * |p| / |g + wd p|`` (1 where either norm is 0); it costs one
+    extra launch for the per-parameter norms.  ``last_norms()`` reads them back."""
+
+    def __init__(self, flat, model, lr, momentum=0.9, weight_decay=0.0, no_decay=(), lars=False, trust_coefficient=0.001):
+        self.flat = flat
+        dev = flat.param_flat.device
+        n = flat.param_flat.numel()
+        self.momentum_buf = torch.zeros(n, device=dev, dtype=torch.float32)
+        self.lr = torch.full((1,), float(lr), device=dev, dtype=torch.float32)
+        self.momentum, self.weight_decay = float(momentum), float(weight_decay)
+        self.lars, self.trust_coefficient = bool(lars), float(trust_coefficient)
+        self.ema = None                      # (``save_checkpoint`` asks: the probe recipe has no EMA)
+        no_decay = set(no_decay)
+        sizes = {nm: p.numel() for nm, p in zip(flat.names, flat._params)}
+        mask = torch.zeros(n, dtype=torch.uint8)
+        for name, off in flat.offsets.items():
+            if name not in no_decay:
+                mask[off:off + sizes[name]] = 1
+        self.decay_mask = mask.to(dev)
+        self.segments = self.partials = self.norms = None
+        if self.lars:
+            table = build_segment_table(flat.names, flat.offsets, {nm: p.shape for nm, p in zip(flat.names, flat._params)})
+            self.segments = table.to(dev)
+            per = int(L.lib().fv_lars_partials_per_segment())      # (a host-side constant of the library)
+            self.partials = torch.zeros(table.shape[0] * 2 * per, device=dev, dtype=torch.float32)
+            self.norms = torch.zeros(table.shape[0], 3, device=dev, dtype=torch.float32)
+
+    def set_lr(self, lr):
+        self.lr.fill_(float(lr))
+
+    def last_norms(self):
+        """LARS: ``{name: (|p|, |dp|, q)}`` of the last step (one device-to-host read; ``step`` never calls it)."""
+        if self.norms is None:
+            raise RuntimeError("FlatSGD was built without lars=True: no norms are computed")
+        return {nm: tuple(r) for nm, r in zip(self.flat.names, self.norms.tolist())}
+
+    # ------------------------------------------------------------------ checkpoint I/O
+    def _named_slices(self, buf):
+        f = self.flat
+        named = dict(zip(f.names, f._params))
+        return {n: buf[o:o + named[n].numel()].view_as(named[n]) for n, o in f.offsets.items()}
+
+    def state_dict(self):
+        """Per-parameter NAMED momentum buffers and the hyper-parameters (``torch.optim.SGD.state_dict()`` by name)."""
+        mu = self._named_slices(self.momentum_buf)
+        return {"state": {n: {"momentum_buffer": v.detach().clone()} for n, v in mu.items()},
+                "lr": float(self.lr.item()), "momentum": self.momentum, "weight_decay": self.weight_decay,
+                "lars": self.lars, "trust_coefficient": self.trust_coefficient}
+
+    def load_state_dict(self, sd):
+        mu = self._named_slices(self.momentum_buf)
+        missing = set(mu) - set(sd["state"])
+        if missing:
+            raise KeyError(f"FlatSGD.load_state_dict: no state for {sorted(missing)[:4]} ...")
+        if bool(sd.get("lars", False)) != self.lars:
+            raise ValueError(f"FlatSGD.load_state_dict: the state was saved with lars={sd.get('lars')}, this optimizer was "
+                             f"built with lars={self.lars}")
+        with torch.no_grad():
+            for n in mu:
+                mu[n].copy_(sd["state"][n]["momentum_buffer"])
+            self.lr.fill_(float(sd["lr"]))
+        self.momentum, self.weight_decay = float(sd["momentum"]), float(sd["weight_decay"])
+        self.trust_coefficient = float(sd.get("trust_coefficient", self.trust_coefficient))
+
+    def step(self, grad_scale=1.0):
+        """``grad_scale``: factor applied to every gradient element as it is read (``1 / world_size`` after a sum
+        all-reduce), as for ``FlatAdamW.step``."""
+        f = self.flat
+        f.finish_backward()
+        n = f.param_flat.numel()
+        st = L.stream_of(f.param_flat)
+        fl = ctypes.c_float
+        if not self.lars:
+            rc = L.lib().fv_sgd_flat(L.ptr(f.param_flat), L.ptr(f.grad_flat), L.ptr(self.momentum_buf), L.ptr(f.shadow_flat),
+                                     L.ptr(self.decay_mask), L.ptr(self.lr), fl(self.momentum), fl(self.weight_decay),
+                                     fl(grad_scale), ctypes.c_size_t(n), st)
+            L.check(rc, "sgd_flat")
+        else:
+            ns = self.segments.shape[0]
+            rc = L.lib().fv_lars_sumsq_partials(L.ptr(f.param_flat), L.ptr(f.grad_flat), L.ptr(self.segments), L.i32(ns),
+                                                L.ptr(self.partials), fl(self.weight_decay), fl(grad_scale),
+                                                ctypes.c_size_t(n), st)
+            L.check(rc, "lars_sumsq_partials")
+            rc = L.lib().fv_lars_flat(L.ptr(f.param_flat), L.ptr(f.grad_flat), L.ptr(self.momentum_buf), L.ptr(f.shadow_flat),
+                                      L.ptr(self.segments), L.i32(ns), L.ptr(self.partials), L.ptr(self.lr), L.ptr(self.norms),
+                                      fl(self.momentum), fl(self.weight_decay), fl(self.trust_coefficient), fl(grad_scale),
+                                      ctypes.c_size_t(n), st)
+            L.check(rc, "lars_flat")
+        f.refresh_transposed()      # (the kernel above has just re-cast the bf16 shadows)
+
+
 def save_checkpoint(path, model, opt, prefix="backbone.", **extra):
     """Write a checkpoint in the layout of the reference's Lightning checkpoints: ``state_dict`` (model keys behind
     ``prefix``: the LightningModule holds the model as ``self.backbone``), ``state_dict_ema`` (when the optimizer tracks an

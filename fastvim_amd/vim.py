@@ -16,6 +16,7 @@ import torch.nn as nn
 from .fastvim import (Block as _FastVimBlock, DropPath, PatchEmbed as _PatchEmbed, _init_weights, segm_init_weights,
                       trunc_normal_)
 from .layernorm import RMSNorm, layer_norm_fn
+from .linear_probe import is_probe_head, probe_head_forward
 from .mamba_simple import Mamba
 from .mamba_simple_faster import linear_module
 
@@ -165,7 +166,7 @@ class VisionMamba(nn.Module):
         x = self.forward_features(x, inference_params)
         if return_features:
             return x
-        x = linear_module(self.head, x)
+        x = probe_head_forward(self.head, x) if (is_probe_head(self.head) and x.is_cuda) else linear_module(self.head, x)
         if self.final_pool_type == "max":
             x = x.max(dim=1)[0]
         return x

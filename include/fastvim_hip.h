@@ -58,7 +58,10 @@ const char* fv_last_error(void);
  *      Later, still 3: two preconditions were RELAXED, nothing added.  fv_patch_unfold and fv_patch_unfold_mix take any
  *      even patch width from 8 up (was: a multiple of 8; patch 14 of FastVim-H / MAE-H), and fv_mixer_combine_fwd / _bwd serve
  *      d_inner 2560 (and the other multiples of 512 from 1536 to 4096 that had no form) with tokens_per_patch > 1 when
- *      there is one patch column (the un-pooled geometry of the masked MAE encoders and the Vim mixer). */
+ *      there is one patch column (the un-pooled geometry of the masked MAE encoders and the Vim mixer).
+ *      Later, still 3: fv_bn1d_stats, fv_bn1d_apply, fv_bn1d_bwd, fv_sgd_flat, fv_lars_partials_per_segment,
+ *      fv_lars_sumsq_partials and fv_lars_flat were ADDED (the linear-probe recipe: BatchNorm1d over pooled features,
+ *      momentum SGD and LARS over the flat buffers). */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -741,6 +744,55 @@ int fv_adamw_flat_groups(float* params, const float* grads, float* exp_avg, floa
                          const float* lr, float* step, const float* partials, int n_partials, const float* max_norm,
                          float* stats, int skip_nonfinite, float beta1, float beta2, float eps, float ema_decay,
                          float grad_scale, size_t n, fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * BatchNorm1d over pooled features (batch, dim), row-major, fp32 or bf16 -- the linear-probe head of the reference
+ * (mae/linear_imagenet.py:39-53: Sequential(BatchNorm1d(dim, affine=False, eps=1e-6), head); a SyncBatchNorm under
+ * mae/linear.py:41).  Statistics, running buffers (fp32) and the counter (int64) as in torch.nn.BatchNorm1d.  All
+ * sums are taken in a fixed order (no atomics): same input, same bits.
+ *
+ * fv_bn1d_stats: table_row (2 dim + 1 floats) = [mean(dim) | M2(dim) | count]: per-column mean and centred sum of
+ *   squares of THIS rank's rows, by exact passes (mean, then deviations from it), and the row count.
+ * fv_bn1d_apply: training != 0: merges the `world` rows of `table` (row r at table + r (2 dim + 1)) in rank order with
+ *   the parallel-variance formula, writes xhat = (x - mean) * rsqrt(M2 / n + eps) in the feature dtype, the merged mean
+ *   and rstd (dim floats each, for fv_bn1d_bwd), and updates running_mean / running_var (nullable, together) with
+ *   `momentum` -- the running variance from M2 / (n - 1) -- and num_batches_tracked (nullable) += 1: each by exactly
+ *   one thread, so a replayed graph advances them once per replay.  training == 0: xhat from the running statistics
+ *   (required), mean_out / rstd_out = what was used, no buffer touched, table unused.
+ * fv_bn1d_bwd: training != 0: dx = rstd (dy - mean_b(dy) - xhat mean_b(dy xhat)) with xhat = (x - mean) rstd recomputed
+ *   from x and the mean / rstd fv_bn1d_apply wrote -- the adjoint for ONE rank's batch statistics.  training == 0:
+ *   dx = dy * rstd.  dy, x, dx share the feature dtype.
+ * ---------------------------------------------------------------------- */
+int fv_bn1d_stats(const void* x, int dtype, float* table_row, int batch, int dim, fv_stream_t stream);
+int fv_bn1d_apply(const void* x, int dtype, const float* table, int world, float* running_mean, float* running_var,
+                  int64_t* num_batches_tracked, void* xhat, float* mean_out, float* rstd_out, int batch, int dim,
+                  float eps, float momentum, int training, fv_stream_t stream);
+int fv_bn1d_bwd(const void* dy, const void* x, int dtype, const float* mean, const float* rstd, void* dx, int batch,
+                int dim, int training, fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Momentum SGD and LARS over the flat buffers of fv_adamw_flat (lr a device scalar; bf16 shadow refreshed in the same
+ * pass, nullable): the linear-probe optimizers (mae/linear_imagenet.py:230 torch.optim.SGD(momentum=0.9); mae/lars.py).
+ *
+ * fv_sgd_flat: g' = g * grad_scale + weight_decay * p (where decay_mask[i] != 0); buf = momentum * buf + g';
+ *   p -= lr * buf.  With a zero-initialised buf: torch.optim.SGD, dampening 0, no Nesterov.  n % 4 == 0.
+ * LARS: `segments` is DEVICE memory, n_segments rows of three int64 (first element, element count, ndim > 1), one per
+ *   parameter; a row that does not lie inside [0, n) is skipped.  P = fv_lars_partials_per_segment().
+ * fv_lars_sumsq_partials: partials (n_segments x 2 x P floats): fixed-order partial sums of |p|^2 and of
+ *   |g * grad_scale + weight_decay * p|^2 of every segment with ndim > 1.
+ * fv_lars_flat: per segment with ndim > 1: finishes its partials, q = trust_coefficient |p| / |dp| when both norms are
+ *   positive, else 1; dp = (g * grad_scale + weight_decay * p) * q.  Segments with ndim <= 1: dp = g * grad_scale
+ *   (lars.py:29).  Then buf = momentum * buf + dp; p -= lr * buf.  norms: NULL, or n_segments x 3 floats written as
+ *   [|p|, |dp|, q] ([0, 0, 1] for ndim <= 1).
+ * ---------------------------------------------------------------------- */
+int fv_sgd_flat(float* params, const float* grads, float* momentum_buf, void* shadow_bf16, const uint8_t* decay_mask,
+                const float* lr, float momentum, float weight_decay, float grad_scale, size_t n, fv_stream_t stream);
+int fv_lars_partials_per_segment(void);
+int fv_lars_sumsq_partials(const float* params, const float* grads, const int64_t* segments, int n_segments,
+                           float* partials, float weight_decay, float grad_scale, size_t n, fv_stream_t stream);
+int fv_lars_flat(float* params, const float* grads, float* momentum_buf, void* shadow_bf16, const int64_t* segments,
+                 int n_segments, const float* partials, const float* lr, float* norms, float momentum,
+                 float weight_decay, float trust_coefficient, float grad_scale, size_t n, fv_stream_t stream);
 
 #ifdef __cplusplus
 }
