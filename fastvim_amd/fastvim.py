@@ -8,7 +8,8 @@ into the reference's Lightning / Hydra ``_target_`` training loops.  Differences
   whose kernels walk the grid with swapped token strides (models/fastvim.py:192-210 does two
   full-length copies per odd layer);
 * DropPath on the mixer branch is a per-sample scale folded into the fused add+RMSNorm kernel;
-* timm / mmdet / mmseg are not imported (``MM_FastVim`` det/seg glue is out of scope).
+* timm / mmdet / mmseg are not imported: ``MM_FastVim`` is the backbone without the registry decorators, its feature
+  taps are one LayerNorm + NCHW launch each (``dense_ops.tap_layer_norm_nchw``); the necks and heads stay with mm*.
 """
 import math
 from functools import partial
@@ -19,6 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch import Tensor
 
+from .dense_ops import tap_layer_norm_nchw
 from .layernorm import RMSNorm, layer_norm_fn, rms_norm_fn
 from .linear_probe import is_probe_head, probe_head_forward
 from . import glue_ops as G
@@ -643,9 +645,21 @@ class MM_FastVim(VisionMamba):
             w = w.transpose(2, 3)
         return torch.flatten(w, 2).transpose(1, 2)
 
+    def _fused_taps(self, outs):
+        """One LayerNorm + NCHW launch per tap (csrc/chan_ln.hip): hidden states on the GPU, embed_dim 192 / 384 / 768,
+        bf16 or fp32, outside the fp16-boundary regime.  Every other case runs the torch composition below."""
+        return (self.embed_dim in (192, 384, 768) and len(outs) > 0
+                and all(o.is_cuda and o.dtype in (torch.float32, torch.bfloat16) for o in outs)
+                and all(getattr(self, f"outnorm_{i}").weight.dtype == torch.float32 for i in range(len(outs))))
+
     def forward(self, x):
         C = self.embed_dim
+        half = msf.half_io(x) or self.pos_embed_dtype_is_half()
         outs, (H, W) = self.forward_features(x, out_indices=self.out_indices)
+        if not half and self._fused_taps(outs):
+            norms = [getattr(self, f"outnorm_{i}") for i in range(len(outs))]
+            outs = [tap_layer_norm_nchw(o, m.weight, m.bias, H, W, m.eps) for o, m in zip(outs, norms)]
+            return outs[0] if len(self.out_indices) == 1 else outs
         outs = [getattr(self, f"outnorm_{i}")(o.float()) for i, o in enumerate(outs)]
         outs = [o.view(-1, H, W, C).permute(0, 3, 1, 2).contiguous() for o in outs]
         return outs[0] if len(self.out_indices) == 1 else outs

@@ -384,6 +384,33 @@ int fv_add_norm_bwd(const void* dy, int dy_dtype, const void* dresidual_out, int
                     int is_rms_norm, fv_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * LayerNorm over C with an NCHW side: the dense-prediction (detection / segmentation) kernels (csrc/chan_ln.hip).
+ *
+ * Feature tap (models/fastvim.py:682-690, outnorm_i + view(-1, H, W, C).permute(0, 3, 1, 2).contiguous()):
+ *   x (B, L, C) token-major, FV_F32 / FV_BF16, L = H * W, token l = cell (l / W, l % W);
+ *   y (B, C, L) fp32 = weight[c] * (x - mean) * rstd + bias[c], statistics over C in fp32; mean, rstd (B * L) fp32.
+ *   C % 4 == 0, 4 <= C <= 1024; x, y, dy, dx, weight, bias 16-byte aligned (any L: plane bases may be unaligned).
+ * Backward: dy (B, C, L) fp32 -> dx (B, L, C) in x's dtype; partial_dw / partial_db (fv_tap_ln_blocks(B, L), C):
+ *   one row per workgroup, reduce with fv_reduce_partials.
+ *
+ * LN2d (detection/vitdet/simple_fpn.py:15-32): x, y, dy, dx contiguous (N, C, HW) of one dtype (FV_F32 / FV_BF16),
+ *   y = weight[c] * (x - mean) * rstd + bias[c] with mean / rstd over C per (n, position), saved as (N * HW) fp32.
+ *   1 <= C <= 1024, any HW >= 1; partial rows: (fv_ln2d_blocks(N, C, HW), C).
+ * The *_blocks queries are host-only and return 0 for shapes the launches refuse.
+ * ---------------------------------------------------------------------- */
+int fv_tap_ln_blocks(int B, int L);
+int fv_tap_ln_fwd(const void* x, int x_dtype, const float* weight, const float* bias, float* y, float* mean,
+                  float* rstd, int B, int L, int C, float eps, fv_stream_t stream);
+int fv_tap_ln_bwd(const float* dy, const void* x, int x_dtype, const float* weight, const float* mean,
+                  const float* rstd, void* dx, float* partial_dw, float* partial_db, int B, int L, int C,
+                  fv_stream_t stream);
+int fv_ln2d_blocks(int N, int C, int HW);
+int fv_ln2d_fwd(const void* x, int dtype, const float* weight, const float* bias, void* y, float* mean, float* rstd,
+                int N, int C, int HW, float eps, fv_stream_t stream);
+int fv_ln2d_bwd(const void* dy, const void* x, int dtype, const float* weight, const float* mean, const float* rstd,
+                void* dx, float* partial_dw, float* partial_db, int N, int C, int HW, fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * bf16 MFMA GEMM  C[M][N] = sum_k A(m,k) B(k,n) (+ bias[n]), fp32 accumulate.
  * Replaces the cuBLAS GEMMs behind in_proj / out_proj (mamba_simple_faster.py:189-193, 435-444),
  * the patch-embed Conv2d (models/fastvim.py:95, k == stride) and their autograd adjoints.
