@@ -146,3 +146,24 @@ def conv_pool_adjoint_ref(x, w_f, b_f, w_b, b_b, D, D_b, d_o, dxc, rows, cols, t
     ((d_o.to(F64) * 0.5 * skip).sum() + (dtot * xc).sum()).backward()
     part = torch.cat([w_f.grad.reshape(-1), w_b.grad.reshape(-1), b_f.grad, b_b.grad, D.grad, D_b.grad])
     return x.grad, part
+
+
+# ------------------------------------------------------------------------------------------------ bounds
+def cpu64(t):
+    return None if t is None else t.detach().double().cpu()
+
+
+def close(errs, name, got, ref, tol, stored_bf16=False, elementwise_scale=False):
+    """Record a violation of |got - ref| <= tol * max(1, max|ref|) (elementwise max(1, |ref|) for the LayerNorm
+    statistics), plus one bf16 storage rounding 2**-8 * |ref| where the kernel stores the tensor in bf16."""
+    got, ref = cpu64(got), ref.detach().double()
+    assert got.shape == ref.shape, (name, got.shape, ref.shape)
+    bound = tol * (ref.abs().clamp_min(1.0) if elementwise_scale else max(1.0, ref.abs().max().item()))
+    if stored_bf16:
+        bound = 2.0 ** -8 * ref.abs() + bound
+    err = (got - ref).abs()
+    worst = (err - bound).argmax()
+    print(f"{name}: max err {err.max().item():.3e}  max|ref| {ref.abs().max().item():.3e}  "
+          f"worst err/bound {(err / bound).max().item():.3f}")
+    if not bool((err <= bound).all()) or not bool(torch.isfinite(got).all()):
+        errs.append((name, err.reshape(-1)[worst].item(), tuple(int(k) for k in torch.unravel_index(worst, err.shape))))

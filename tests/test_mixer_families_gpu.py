@@ -363,24 +363,7 @@ def lib():
     return _lib.lib()
 
 
-def _cpu(t):
-    return None if t is None else t.detach().double().cpu()
-
-
-def _close(errs, name, got, ref, tol, stored_bf16=False, elementwise_scale=False):
-    """Record a violation of |got - ref| <= tol * max(1, max|ref|) (elementwise max(1, |ref|) for the LayerNorm
-    statistics), plus one bf16 storage rounding 2**-8 * |ref| where the kernel stores the tensor in bf16."""
-    got, ref = _cpu(got), ref.detach().double()
-    assert got.shape == ref.shape, (name, got.shape, ref.shape)
-    bound = tol * (ref.abs().clamp_min(1.0) if elementwise_scale else max(1.0, ref.abs().max().item()))
-    if stored_bf16:
-        bound = BF16_HALF_ULP * ref.abs() + bound
-    err = (got - ref).abs()
-    worst = (err - bound).argmax()
-    print(f"{name}: max err {err.max().item():.3e}  max|ref| {ref.abs().max().item():.3e}  "
-          f"worst err/bound {(err / bound).max().item():.3f}")
-    if not bool((err <= bound).all()) or not bool(torch.isfinite(got).all()):
-        errs.append((name, err.reshape(-1)[worst].item(), tuple(int(k) for k in torch.unravel_index(worst, err.shape))))
+_cpu, _close = R.cpu64, R.close      # the bound helper lives in mixer_family_ref.py (test_fused_proj_gpu.py uses it too)
 
 
 def _names(family):
