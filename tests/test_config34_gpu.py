@@ -262,7 +262,9 @@ def _scan_cl_case(Bsz, Lc, d_in, R, dtype, seed):
                                            (2, 1000, 768, 4),       # d_inner != 32 dt_rank (explicit dt_rank), segment-parallel:
                                                                     # segments / chunks / partial rows from the REAL d_inner
                                            (64, 37, 384, 12),       # enough workgroups for the 12-wave form (192 channels)
-                                           (64, 14, 1536, 48),      # short kernel walking 4 batch elements per workgroup
+                                           (64, 14, 1536, 48),      # short kernel walking 2 batch elements per workgroup (8 channel
+                                                                    # chunks x 16 x 2 = 256 workgroups < 512: not 4; NBB 4 / 8 are
+                                                                    # launched by test_scan_cl_plans_gpu.py)
                                            (2, 40, 1024, 64)])      # dt_rank > 48: the generic kernel (4-step segments)
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("given", [False, True])
