@@ -21,7 +21,9 @@
 //            are requested before the K loop;
 //   phase 3  gemm_dgrad_addnorm_bwd_kernel<64>'s epilogue from the product tile on, lane for lane (d hidden and d residual
 //            bit-identical for the same d xz; the norm weight's row sums are grouped per pooling-row tile);
-//   phase 4  d g of the previous block = d x tile @ W_out, tile_times_w2's code with the tile's row map.
+//   phase 4  d g of the previous block = d x tile @ W_out, tile_times_w2's code with the tile's row map (PK2: wave w owns
+//            d g columns [96 w, 96 w + 96) and streams its quarter of W_out's fragment-major copy from L2 straight into
+//            operand registers like phase 2 -- no LDS weight stage, no transposing read, no barrier in the K loop).
 // d xz's x half is read back by the weight gradient only: 19.3 MB of reads, one launch boundary and the cold start of a
 // 392-workgroup GEMM per block go away.  LDS: 75 KB per workgroup, two workgroups per CU.
 #include "mixer_common.h"
@@ -42,6 +44,12 @@ constexpr int CD_RSB = CD_N * 2 + 16;          // product tile row stride of the
 #ifndef CD_W2_PIPE
 #define CD_W2_PIPE 1     // second phase: the next panel's first weight stage requested before this panel's epilogue
 #endif
+#ifndef CD_W2_PASSES
+#define CD_W2_PASSES 1   // PK2 second phase: a wave's 96 d g columns in one pass (96 accumulator registers) or two of 48
+#endif
+#ifndef CD_W2_PDEPTH
+#define CD_W2_PDEPTH 3   // PK2 second phase: k steps (6 KiB of weight fragments each) in flight per wave
+#endif
 constexpr int CD_PD = CD_PDEPTH;               // k steps of weight fragments in flight per wave (refilled in line pairs)
 constexpr int CD_KS = CD_K / 32;               // 24 k steps; 0..11 the x half (panel), 12..23 the z half (ring)
 constexpr int CD_ZST = CD_BM * BK * 2;         // one z stage: 64 rows x 64 k, bf16, [row][64] with the KC chunk swizzle
@@ -56,8 +64,16 @@ static_assert(2 * CD_SMEM <= 160 * 1024, "two workgroups per CU");
 #define CD_FORCE_PK 0  // timing probe: the plain entry point streams its weight with the packed addressing (values are wrong)
 #endif
 #ifndef CD_DBG
-#define CD_DBG 0      // phase probes (tuning): 1 no conv arithmetic, 2 no K loop, 3 no epilogue, 4 no second phase
-#endif
+#define CD_DBG 0      // phase probes (tuning): 1 no conv arithmetic, 2 no K loop, 3 no epilogue, 4 no second phase,
+#endif                //                        5 (PK2) second phase without its d g stores
+// PK2 second phase: K = 192 is 6 k steps; a wave's 96 columns are 6 column blocks, CD_W2_NBP of them per pass
+constexpr int CD_W2_KS = CD_N / 32, CD_W2_P = CD_W2_PASSES, CD_W2_NBP = 6 / CD_W2_P, CD_W2_STEPS = CD_W2_KS * CD_W2_P;
+constexpr int CD_W2_RING = CD_W2_PDEPTH * CD_W2_P;        // ring slots (one step of a pass each): the same bytes in flight
+constexpr int CD_W2_RS = CD_W2_NBP * 32 + 16;             // slab row stride (bytes): = 4 r (mod 64) dwords over 16 rows, conflict-free
+constexpr int CD_W2_ROWS = 16 * CD_W2_P;                  // tile rows per slab round: three 16-byte stores per lane either way
+static_assert(CD_W2_P == 1 || CD_W2_P == 2, "one pass of 96 columns or two of 48");
+static_assert(CD_W2_RING >= 1 && CD_W2_RING <= CD_W2_STEPS, "ring depth");
+static_assert(CD_W2_ROWS * CD_W2_RS <= 32 * (64 * 2 + 16), "the wave's slab");
 
 struct CdParams {
   // ---- conv + pool adjoint (fvi::BwdParams of fv_mixer_conv_pool_bwd2)
@@ -83,7 +99,8 @@ struct CdParams {
   bf16_t* dx;              // (M, 192) d hidden (x row_scale)
   float* dres_in;          // (M, 192)
   float* pw;               // (workgroups, 192) partial sums of d norm weight
-  const bf16_t* W2;        // (192, ldw2): previous block's out_proj.weight as stored, nullable
+  const bf16_t* W2;        // (192, ldw2): previous block's out_proj.weight as stored, nullable; PK2: its fragment-major copy
+                           // (fv_pack_weight_frags_w2_batched), not null
   long ldw2;
   bf16_t* C2;              // (M, N2) d g of the previous block
   int N2;
@@ -110,7 +127,10 @@ static_assert(cd_younger(3) < 64 && cd_younger(4) < 64 && cd_younger(5) < 64, "v
 // PK: the weight is the fragment-major copy -- 16-byte unit ((wv * 24 + ks) * 3 + nb) * 64 + lane is the fragment lane `lane`
 // of wave wv feeds the MFMAs of column block nb at k step ks, so a load instruction reads 1 KiB contiguous and a wave's whole
 // stream is one 72 KB run.  Only the address of a load differs from the plain form.
-template <int NT, bool X2, bool PK>
+// PK2: W2 is the fragment-major copy of out_proj.weight for the K-slow product of phase 4 -- 16-byte unit
+// ((wv * 6 + ks) * 6 + nb) * 64 + lane holds W_out[32 ks + 8 (lane >> 4) + j][96 wv + 16 nb + (lane & 15)], j = 0..7: what
+// the transposing LDS read of the plain form (KsFrags::get) hands lane `lane` for that column block and k step.
+template <int NT, bool X2, bool PK, bool PK2 = false>
 __global__ __launch_bounds__(CD_NT, 2) void conv_pool_bwd_dgrad_kernel(CdParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef PairVec<bf16_t, 1> P;
@@ -449,6 +469,20 @@ __global__ __launch_bounds__(CD_NT, 2) void conv_pool_bwd_dgrad_kernel(CdParams 
     }
   __syncthreads();
   if (CD_DBG == 3) return;
+  // PK2: this wave's stream of the second weight and the ring its fragments wait in
+  bf16x8 w2f[PK2 ? CD_W2_RING : 1][CD_W2_NBP];
+  const char* w2pk = reinterpret_cast<const char*>(p.W2) + wv * (CD_W2_KS * 6 * 1024);      // (uniform)
+  auto w2frag = [&](int a, int s) {           // column block a of step s (pass s / 6, k step s % 6)
+    return *reinterpret_cast<const bf16x8*>(w2pk + ((s % CD_W2_KS) * 6 + (s / CD_W2_KS) * CD_W2_NBP + a) * 1024 + (uint32_t)lane * 16);
+  };
+  auto w2prefill = [&]() {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < CD_W2_RING; ++s)
+#pragma unroll
+      for (int a = 0; a < CD_W2_NBP; ++a) w2f[s][a] = w2frag(a, s);
+    __builtin_amdgcn_sched_barrier(0);
+  };
   {
     // (the norm kernels are built without the denormal flush and with source-order arithmetic where it matters: keep
     //  this block's contraction choices those of gemm_mfma.hip)
@@ -523,6 +557,9 @@ __global__ __launch_bounds__(CD_NT, 2) void conv_pool_bwd_dgrad_kernel(CdParams 
         }
       }
     }
+    // the first ring slots are requested here and arrive under the norm weight's reduction (requested in front of phase 3
+    // they slow its rows down by more than the K loop gains: 59.5 against 58.8 us per launch)
+    if constexpr (PK2 && CD_DBG != 4) w2prefill();
     // d norm weight: the 4 row groups of a wave (permlane swaps), then the 4 waves through LDS, fixed order
     __syncthreads();
     float* s_acc = reinterpret_cast<float*>(smem + CD_BM * CD_RSB);
@@ -542,7 +579,64 @@ __global__ __launch_bounds__(CD_NT, 2) void conv_pool_bwd_dgrad_kernel(CdParams 
     for (int c = tid; c < CD_N; c += CD_NT) dst[c] = (s_acc[c] + s_acc[CD_N + c]) + (s_acc[2 * CD_N + c] + s_acc[3 * CD_N + c]);
   }
   // ================= phase 4: the previous block's out_proj data gradient d g = d x @ W_out from the tile in LDS =================
-  if (p.W2 && CD_DBG != 4) {
+  if constexpr (PK2) {
+    // Every wave reads the whole d x tile (its rows were published by the barrier in front of the norm weight's
+    // reduction) and owns 96 columns; the slabs lie behind the reduction's scratch, so no barrier is needed here.
+    if (CD_DBG == 4) return;
+    char* my = smem + CD_O_S + wv * (32 * (64 * 2 + 16));
+    const char* afrag = smem + (lane & 15) * CD_RSB + (lane >> 4) * 16;
+    f32x4 acc[CD_W2_NBP][4];
+    static_for<CD_W2_STEPS>([&](auto s_c) {
+      constexpr int s = decltype(s_c)::value, ks = s % CD_W2_KS, pass = s / CD_W2_KS;
+      if constexpr (ks == 0) {
+#pragma unroll
+        for (int a = 0; a < CD_W2_NBP; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+      bf16x8 cur[CD_W2_NBP];
+#pragma unroll
+      for (int a = 0; a < CD_W2_NBP; ++a) cur[a] = w2f[s % CD_W2_RING][a];
+      if constexpr (s + CD_W2_RING < CD_W2_STEPS) {
+#pragma unroll
+        for (int a = 0; a < CD_W2_NBP; ++a) w2f[s % CD_W2_RING][a] = w2frag(a, s + CD_W2_RING);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      bf16x8 fa[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) fa[b] = *reinterpret_cast<const bf16x8*>(afrag + b * 16 * CD_RSB + ks * 64);
+#pragma unroll
+      for (int a = 0; a < CD_W2_NBP; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur[a], fa[b], acc[a][b], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (ks == CD_W2_KS - 1) {
+        // bf16 through the wave's slab: 16-byte stores, a row's 96 (48) columns as one run
+        //      acc[a][b][j] = d g[tile row b * 16 + (lane & 15)][96 wv + 16 (pass * NBP + a) + (lane >> 4) * 4 + j]
+        constexpr int CH = CD_W2_NBP * 2;
+#pragma unroll
+        for (int h = 0; h < 64 / CD_W2_ROWS; ++h) {
+#pragma unroll
+          for (int bb = 0; bb < CD_W2_P; ++bb)
+#pragma unroll
+            for (int a = 0; a < CD_W2_NBP; ++a) {
+              const f32x4 v = acc[a][h * CD_W2_P + bb];
+              uint2 pk = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+              *reinterpret_cast<uint2*>(my + (bb * 16 + (lane & 15)) * CD_W2_RS + (a * 16 + (lane >> 4) * 4) * 2) = pk;
+            }
+          __builtin_amdgcn_wave_barrier();
+#pragma unroll
+          for (int i = 0; i < CD_W2_ROWS * CH / 64; ++i) {
+            const int idx = i * 64 + lane, r = idx / CH, ch = idx - r * CH;
+            const int m = tok_of(h * CD_W2_ROWS + r), n = wv * 96 + pass * (CD_W2_NBP * 16) + ch * 8;
+            if (CD_DBG == 5 ? m == -2 : m >= 0)
+              *reinterpret_cast<u32x4*>(p.C2 + (long)m * CD_DI + n) = *reinterpret_cast<const u32x4*>(my + r * CD_W2_RS + ch * 16);
+          }
+          __builtin_amdgcn_wave_barrier();
+        }
+      }
+    });
+  } else if (p.W2 && CD_DBG != 4) {
     __syncthreads();
     tile_times_w2_rows<CD_BM, CD_RSB, KS, decltype(tok_of), CD_W2_PIPE != 0>(smem, smem + CD_O_B, smem + CD_O_S, p.W2, p.ldw2, p.N2,
                                                                               p.C2, tok_of, tid);
@@ -561,8 +655,9 @@ extern "C" int fv_mixer_conv_pool_bwd_dgrad_ok(int batch, int rows, int cols, in
 
 extern "C" int fv_mixer_conv_pool_bwd_dgrad_blocks(int batch, int rows) { return batch * fv_cdiv(rows, 4); }
 
+// packed: 0 plain weights, 1 W_in_t fragment-major, 2 W_in_t and W2 fragment-major
 static int cd_launch(
-    bool packed, const void* xz, const void* dskip, const float* dxc, const void* dxc2, const float* conv_w, const float* conv_b,
+    int packed, const void* xz, const void* dskip, const float* dxc, const void* dxc2, const float* conv_w, const float* conv_b,
     const float* conv_w_b, const float* conv_b_b, const float* D, const float* D_b, void* dxz, float* conv_partials, int batch,
     int rows, int cols, int tok_stride_row, int tok_stride_col, float scaling, const void* W_in_t, long ldwt,
     const float* dresidual_out, const float* r, const float* rstd, const float* norm_weight, const float* row_scale,
@@ -581,6 +676,8 @@ static int cd_launch(
                ((uintptr_t)norm_weight & 15) == 0 && ((uintptr_t)dresidual_out & 15) == 0 && ((uintptr_t)dxz & 15) == 0,
            "mixer_conv_pool_bwd_dgrad: row operands must be 16-byte aligned");
   FV_CHECK(!row_scale || rows_per_scale > 0, "mixer_conv_pool_bwd_dgrad: rows_per_scale must be positive");
+  FV_CHECK(packed != 2 || (W2 && C2 && N2 == CD_DI && ldw2 == CD_DI),
+           "mixer_conv_pool_bwd_dgrad_pk2: the packed second weight is (192, %d) without row padding, and not null", CD_DI);
   FV_CHECK(!W2 || (C2 && N2 > 0 && N2 % 128 == 0 && ldw2 % 8 == 0 && ldw2 >= N2 && ((uintptr_t)W2 & 15) == 0 && ((uintptr_t)C2 & 15) == 0),
            "mixer_conv_pool_bwd_dgrad: the second weight must be (192, N2) with N2 a multiple of 128, 16-byte aligned");
   CdParams p{};
@@ -594,14 +691,19 @@ static int cd_launch(
   p.dres_in = dresidual_in; p.pw = partial_dw; p.W2 = (const bf16_t*)W2; p.ldw2 = ldw2; p.C2 = (bf16_t*)C2; p.N2 = N2;
   p.M = batch * rows * cols;
   const dim3 grid(batch * fv_cdiv(rows, 4)), block(CD_NT);
-#define FV_CD(NTT, XX, PP)                                                                                          \
+#define FV_CD(NTT, XX, PP, P2)                                                                                      \
   do {                                                                                                              \
     static FvOncePerDevice done;                                                                                    \
     if (done.first())                                                                                               \
-      (void)hipFuncSetAttribute((const void*)conv_pool_bwd_dgrad_kernel<NTT, XX, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, CD_SMEM); \
-    hipLaunchKernelGGL((conv_pool_bwd_dgrad_kernel<NTT, XX, PP>), grid, block, CD_SMEM, (hipStream_t)stream, p);    \
+      (void)hipFuncSetAttribute((const void*)conv_pool_bwd_dgrad_kernel<NTT, XX, PP, P2>, hipFuncAttributeMaxDynamicSharedMemorySize, CD_SMEM); \
+    hipLaunchKernelGGL((conv_pool_bwd_dgrad_kernel<NTT, XX, PP, P2>), grid, block, CD_SMEM, (hipStream_t)stream, p); \
   } while (0)
-#define FV_CD2(NTT, XX) do { if (packed || CD_FORCE_PK) FV_CD(NTT, XX, true); else FV_CD(NTT, XX, false); } while (0)
+#define FV_CD2(NTT, XX)                                              \
+  do {                                                               \
+    if (packed == 2) FV_CD(NTT, XX, true, true);                     \
+    else if (packed || CD_FORCE_PK) FV_CD(NTT, XX, true, false);     \
+    else FV_CD(NTT, XX, false, false);                               \
+  } while (0)
   if (cols == 14) { if (dxc2) FV_CD2(14, true); else FV_CD2(14, false); }
   else { if (dxc2) FV_CD2(16, true); else FV_CD2(16, false); }
 #undef FV_CD2
@@ -622,7 +724,11 @@ static int cd_launch(
       tok_stride_col, scaling, W_in_t, ldwt, dresidual_out, r, rstd, norm_weight, row_scale, rows_per_scale, dx,              \
       dresidual_in, partial_dw, W2, C2, N2, ldw2, stream
 
-extern "C" int fv_mixer_conv_pool_bwd_dgrad(CD_ARGS_DECL) { return cd_launch(false, CD_ARGS); }
+extern "C" int fv_mixer_conv_pool_bwd_dgrad(CD_ARGS_DECL) { return cd_launch(0, CD_ARGS); }
 
 // W_in_t is the fragment-major copy of in_proj.weight^T (fv_pack_weight_frags_batched, K = 768); ldwt must be 768
-extern "C" int fv_mixer_conv_pool_bwd_dgrad_pk(CD_ARGS_DECL) { return cd_launch(true, CD_ARGS); }
+extern "C" int fv_mixer_conv_pool_bwd_dgrad_pk(CD_ARGS_DECL) { return cd_launch(1, CD_ARGS); }
+
+// ... and W2 the fragment-major copy of the previous block's out_proj.weight for the K-slow product
+// (fv_pack_weight_frags_w2_batched): not null, N2 = ldw2 = 384
+extern "C" int fv_mixer_conv_pool_bwd_dgrad_pk2(CD_ARGS_DECL) { return cd_launch(2, CD_ARGS); }

@@ -509,6 +509,27 @@ __global__ __launch_bounds__(256) void pack_weight_frags_kernel(PackJobs J) {
   J.dst[blockIdx.y][u] = J.src[blockIdx.y][row * (J.ks_n * 4) + unit_in_row];
 }
 
+// Fragment-major copies of up to 64 weights (192, 384) for the product in which the weight's ROWS are k (out_proj.weight as
+// the operand of its data gradient, phase 4 of fv_mixer_conv_pool_bwd_dgrad_pk2): the 16-byte unit
+//   u = ((wv * 6 + ks) * 6 + nb) * 64 + lane   holds   src[32 ks + 8 (lane >> 4) + j][96 wv + 16 nb + (lane & 15)], j = 0..7
+// (fastvim_amd.mixer_ops.pack_index_w2 is the same map).  A thread moves one unit: the writes are contiguous, the reads
+// gather 8 rows at a 768-byte stride straight from the plain shadow.
+constexpr int PKW2_N = 384, PKW2_UNITS = PKW_ROWS * PKW2_N / 8;
+struct PackJobsW2 {
+  const uint16_t* src[TRJ_MAX];
+  uint4* dst[TRJ_MAX];
+};
+__global__ __launch_bounds__(256) void pack_weight_frags_w2_kernel(PackJobsW2 J) {
+  const int u = blockIdx.x * 256 + threadIdx.x;
+  if (u >= PKW2_UNITS) return;
+  const int lane = u & 63, t = u >> 6, nb = t % 6, ks = (t / 6) % 6, wv = t / 36;
+  const uint16_t* s = J.src[blockIdx.y] + (32 * ks + 8 * (lane >> 4)) * PKW2_N + 96 * wv + 16 * nb + (lane & 15);
+  uint32_t w[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) w[j] = (uint32_t)s[(2 * j) * PKW2_N] | ((uint32_t)s[(2 * j + 1) * PKW2_N] << 16);
+  J.dst[blockIdx.y][u] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // Bytes per tile store of the even-width unfold forms.  Chunks of `gjc` patches start at patch (b*gh + gi)*gw + k*gjc and
 // hold gjc or gw - k*gjc patches: every start and length is a multiple of gcd(gw, gjc) patches of `patch_bytes` each
 // (a multiple of 4: the width is even, an element at least 2 bytes), and `out` itself is 16-byte aligned.
@@ -772,6 +793,22 @@ extern "C" int fv_pack_weight_frags_batched(const void* const* srcs, void* const
   }
   J.ks_n = K / 32;
   hipLaunchKernelGGL(pack_weight_frags_kernel, dim3(fv_cdiv(PKW_ROWS * J.ks_n * 4, 256), njobs), dim3(256), 0, (hipStream_t)stream, J);
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
+// dsts[j] = the fragment-major copy of srcs[j] ((192, 384) bf16 row-major, rows = k) that
+// fv_mixer_conv_pool_bwd_dgrad_pk2 streams in its second phase
+extern "C" int fv_pack_weight_frags_w2_batched(const void* const* srcs, void* const* dsts, int njobs, fv_stream_t stream) {
+  FV_CHECK(srcs && dsts && njobs > 0 && njobs <= TRJ_MAX, "pack_weight_frags_w2_batched: 1..%d jobs", TRJ_MAX);
+  PackJobsW2 J{};
+  for (int j = 0; j < njobs; ++j) {
+    FV_CHECK(srcs[j] && dsts[j] && srcs[j] != dsts[j], "pack_weight_frags_w2_batched: null or aliased pointer in job %d", j);
+    FV_CHECK(((uintptr_t)srcs[j] & 1) == 0 && ((uintptr_t)dsts[j] & 15) == 0, "pack_weight_frags_w2_batched: job %d is not aligned", j);
+    J.src[j] = (const uint16_t*)srcs[j];
+    J.dst[j] = (uint4*)dsts[j];
+  }
+  hipLaunchKernelGGL(pack_weight_frags_w2_kernel, dim3(fv_cdiv(PKW2_UNITS, 256), njobs), dim3(256), 0, (hipStream_t)stream, J);
   FV_LAUNCH_CHECK();
   return FV_OK;
 }

@@ -42,7 +42,8 @@ def _drop_derived_shadows(model):
     state's copies read in its place (the fused optimizer does not bump ``_version``, so the version check alone would
     not catch them)."""
     for p in model.parameters():
-        for a in ("_fv_shadow_t", "_fv_shadow_t_version", "_fv_shadow_pk", "_fv_shadow_pk_version"):
+        for a in ("_fv_shadow_t", "_fv_shadow_t_version", "_fv_shadow_pk", "_fv_shadow_pk_version",
+                  "_fv_shadow_pk2", "_fv_shadow_pk2_version"):
             if hasattr(p, a):
                 delattr(p, a)
     for mod in model.modules():
@@ -180,7 +181,17 @@ class FlatTrainingState:
                 w = getattr(getattr(mod, "out_proj", None), "weight", None)
                 if w is not None and tuple(w.shape) == (192, 384) and w.requires_grad and getattr(w, "_fv_shadow", None) is not None:
                     self._add_packed(384, w, w._fv_shadow)
-        self._pk_dst = self._pk_jobs[768][1] + self._pk_jobs[384][1]
+        # ... and of the same out_proj shadows as the K-slow operand of their data gradient, the second phase of the fused
+        # backward launch (mixer_ops.pack_index_w2): one more launch, straight from the plain shadow
+        self._pk2_src, self._pk2_dst, self._pk2_params = [], [], []
+        for w, src in zip(self._pk_jobs[384][2], self._pk_jobs[384][0]):
+            pk2 = torch.empty(192 * 384, device=dev, dtype=shadow_dtype)
+            w._fv_shadow_pk2 = pk2
+            w._fv_shadow_pk2_version = -1
+            self._pk2_src.append(src)
+            self._pk2_dst.append(pk2)
+            self._pk2_params.append(w)
+        self._pk_dst = self._pk_jobs[768][1] + self._pk_jobs[384][1] + self._pk2_dst
         # ... and of the x_proj weight pairs of the wide models (d_inner >= 768), (2, W, d_inner) -> (2, d_inner, W): the
         # x_proj adjoint's data half streams them K-contiguous into the bf16 matrix cores (fv_mixer_xproj_bwd3)
         self._tx_src, self._tx_dst, self._tx_params = [], [], []
@@ -284,9 +295,9 @@ class FlatTrainingState:
 
     def refresh_transposed(self):
         """Re-make the transposed in_proj shadows from ``shadow_flat`` (one launch) and then the fragment-major copies of
-        them and of the out_proj shadows (one launch per shape); called after every shadow refresh: here and by the fused
-        optimizer step."""
-        from .mixer_ops import pack_weight_frags, transpose_bf16_batched
+        them and of the out_proj shadows (one launch per shape and operand role); called after every shadow refresh: here
+        and by the fused optimizer step."""
+        from .mixer_ops import pack_weight_frags, pack_weight_frags_w2, transpose_bf16_batched
         for src, dst, params in ((self._t_src, self._t_dst, self._t_params),
                                  (getattr(self, "_tx_src", []), getattr(self, "_tx_dst", []), getattr(self, "_tx_params", []))):
             if src:
@@ -298,6 +309,10 @@ class FlatTrainingState:
                 pack_weight_frags(srcs, dsts)
                 for p in params:
                     p._fv_shadow_pk_version = p._version
+        if getattr(self, "_pk2_src", []):
+            pack_weight_frags_w2(self._pk2_src, self._pk2_dst)
+            for p in self._pk2_params:
+                p._fv_shadow_pk2_version = p._version
 
     @property
     def world_size(self):

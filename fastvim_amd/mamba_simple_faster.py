@@ -62,21 +62,23 @@ def use_packed_weights(on):
     return was
 
 
-def _shadow_pk(w, cdt, plain):
+def _shadow_pk(w, cdt, plain, attr="_fv_shadow_pk", pack=None):
     """The FRAGMENT-MAJOR compute-dtype copy FlatTrainingState keeps of an eligible weight (in_proj.weight^T, out_proj.weight:
     ``mixer_ops.pack_index``), or None when there is none or it is switched off: the caller then takes the plain weight,
     exactly as without a flat training state.  ``plain`` is the current plain copy it is a permutation of (``_shadow_t`` /
     ``_shadow`` of the same weight, already refreshed): an in-place write to the parameter since the state last re-made the
-    copy (version counter) is caught here and the copy re-packed from it, like ``_shadow_t``."""
-    pk = getattr(w, "_fv_shadow_pk", None)
+    copy (version counter) is caught here and the copy re-packed from it, like ``_shadow_t``.  ``attr`` / ``pack``: which
+    copy and its pack launch -- ``_fv_shadow_pk2`` / ``M.pack_weight_frags_w2`` for out_proj.weight as the operand of its data
+    gradient (``mixer_ops.pack_index_w2``)."""
+    pk = getattr(w, attr, None)
     if pk is None or pk.dtype != cdt or not _PackedWeights.enabled:
         return None
-    if w._version != w._fv_shadow_pk_version:
+    if w._version != getattr(w, attr + "_version"):
         if not (plain.is_contiguous() and plain.numel() == pk.numel()):
             return None
         with torch.no_grad():
-            M.pack_weight_frags([plain], [pk])
-        w._fv_shadow_pk_version = w._version
+            (pack or M.pack_weight_frags)([plain], [pk])
+        setattr(w, attr + "_version", w._version)
     return pk
 
 
@@ -528,9 +530,12 @@ class ChainedBlockFn(torch.autograd.Function):
             d_prev = g_prev.shape[2]
             W2 = _shadow(W_out_prev, cdt) if d_prev % 128 == 0 else None
             W_in_t = _shadow_t(ctx.W_in, cdt)                # (held across the launch, see _out_proj_add_norm_fwd)
+            W_in_pk = _shadow_pk(ctx.W_in, cdt, W_in_t)
+            W2_pk = (_shadow_pk(W_out_prev, cdt, W2, "_fv_shadow_pk2", M.pack_weight_frags_w2)
+                     if W2 is not None and W_in_pk is not None else None)
             p2, dx, dres_in, pw, nb, dg_prev = M.conv_pool_bwd_dgrad(
                 xz, d_o, dxc, dxc2, cw2, cb, cwb2, cb_b, D, D_b, dxz, rows, cols, transposed, scaling, W_in_t, gg, r, rstd,
-                w32, row_scale, ctx.rows_per_scale, W2=W2, conv_grad_out=conv_grad_out, W_in_pk=_shadow_pk(ctx.W_in, cdt, W_in_t))
+                w32, row_scale, ctx.rows_per_scale, W2=W2, conv_grad_out=conv_grad_out, W_in_pk=W_in_pk, W2_pk=W2_pk)
             out.update(dx=dx, dres_in=dres_in, pw=pw, nb=nb, dg_prev=dg_prev)
             return p2
 

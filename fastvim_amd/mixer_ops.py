@@ -390,12 +390,14 @@ def conv_pool_bwd_dgrad_ok(xz, rows, cols, tpp, d_model, pool_max):
 
 def conv_pool_bwd_dgrad(xz, d_o, dxc, dxc2, conv_w, conv_b, conv_w_b, conv_b_b, D, D_b, dxz, rows, cols, transposed, scaling,
                         W_in_t, dres_out, r, rstd, norm_w32, row_scale, rows_per_scale, W2=None, conv_grad_out=None,
-                        W_in_pk=None):
+                        W_in_pk=None, W2_pk=None):
     """``conv_pool_bwd`` (x half of ``dxz`` written, its z half read) AND ``fv_gemm_bf16_dgrad_addnorm_bwd2`` on the result in
     one launch (fv_mixer_conv_pool_bwd_dgrad).  ``W_in_t`` (d, 2 d_in) bf16 = in_proj.weight^T.  Returns
     (conv parameter-gradient sums or None when accumulated into ``conv_grad_out``, dx (M, d) bf16, dres_in (M, d) fp32,
     pw (nb, d) partial sums of the norm weight's gradient, nb, dg_prev (M, N2) bf16 or None).  ``W_in_pk``: the
-    fragment-major copy of ``W_in_t`` (``pack_weight_frags``); every output stays bit-identical."""
+    fragment-major copy of ``W_in_t`` (``pack_weight_frags``); ``W2_pk`` (with ``W_in_pk`` and ``W2`` (192, 384) only): the
+    fragment-major copy of ``W2`` for the second phase (``pack_weight_frags_w2``) -- without it the plain second phase
+    runs; every output stays bit-identical."""
     B, Ltok, two_d = xz.shape
     d_in = two_d // 2
     d = W_in_t.shape[0]
@@ -410,19 +412,24 @@ def conv_pool_bwd_dgrad(xz, d_o, dxc, dxc2, conv_w, conv_b, conv_w_b, conv_b_b, 
     pw = torch.empty(nb, d, device=dev, dtype=torch.float32)
     N2 = W2.shape[1] if W2 is not None else 0
     dg_prev = torch.empty(Mrows, N2, device=dev, dtype=torch.bfloat16) if W2 is not None else None
+    W2_arg, ldw2 = W2, (W2.stride(0) if W2 is not None else 0)
     assert dxc2 is None or (dxc2.dtype == xz.dtype and dxc2.shape == dxc.shape and dxc2.is_contiguous())
     assert W_in_t.dtype == torch.bfloat16 and W_in_t.stride(1) == 1 and W_in_t.shape[1] == two_d
     if W_in_pk is not None:
         assert W_in_pk.dtype == torch.bfloat16 and W_in_pk.is_contiguous() and W_in_pk.numel() == d * two_d
         fn, W_arg, ldwt = lib.fv_mixer_conv_pool_bwd_dgrad_pk, W_in_pk, two_d
+        if W2_pk is not None and W2 is not None:
+            assert tuple(W2.shape) == (PACK_ROWS, PACK_W2_N) and W2_pk.dtype == torch.bfloat16 and W2_pk.is_contiguous()
+            assert W2_pk.numel() == W2.numel()
+            fn, W2_arg, ldw2 = lib.fv_mixer_conv_pool_bwd_dgrad_pk2, W2_pk, PACK_W2_N
     else:
         fn, W_arg, ldwt = lib.fv_mixer_conv_pool_bwd_dgrad, W_in_t, W_in_t.stride(0)
     rc = fn(
         L.ptr(xz), L.ptr(d_o), L.ptr(dxc), L.ptr(dxc2), L.ptr(conv_w), L.ptr(conv_b), L.ptr(conv_w_b), L.ptr(conv_b_b),
         L.ptr(D), L.ptr(D_b), L.ptr(dxz), L.ptr(part), L.i32(B), L.i32(rows), L.i32(cols), L.i32(s_i), L.i32(s_j),
         f32(scaling), L.ptr(W_arg), ctypes.c_long(ldwt), L.ptr(dres_out), L.ptr(r), L.ptr(rstd), L.ptr(norm_w32),
-        L.ptr(row_scale), L.i32(rows_per_scale), L.ptr(dx), L.ptr(dres_in), L.ptr(pw), L.ptr(W2), L.ptr(dg_prev), L.i32(N2),
-        ctypes.c_long(W2.stride(0) if W2 is not None else 0), L.stream_of(xz))
+        L.ptr(row_scale), L.i32(rows_per_scale), L.ptr(dx), L.ptr(dres_in), L.ptr(pw), L.ptr(W2_arg), L.ptr(dg_prev), L.i32(N2),
+        ctypes.c_long(ldw2), L.stream_of(xz))
     L.check(rc, "mixer_conv_pool_bwd_dgrad")
     if conv_grad_out is not None:
         reduce_partials(part, nb, out=conv_grad_out, accumulate=True)
@@ -485,6 +492,44 @@ def pack_weight_frags(srcs, dsts):
         ins = (ctypes.c_void_p * k)(*[t.data_ptr() for t in a])
         outs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in b])
         L.check(lib.fv_pack_weight_frags_batched(ins, outs, L.i32(k), L.i32(K), L.stream_of(a[0])), "pack_weight_frags_batched")
+
+
+PACK_W2_N = 384     # d g columns of the fused backward launch's second phase: four waves x six 16-column MFMA blocks
+
+
+def pack_index_w2():
+    """The fragment-major layout of ``out_proj.weight`` (192, 384) as the K-SLOW operand of its data gradient (second phase
+    of fv_mixer_conv_pool_bwd_dgrad_pk2: rows are k), as a gather: a (192 * 384 / 8, 8, 2) int64 tensor whose entry
+    ``[u, j]`` is (row, column) of element ``j`` of the 16-byte unit ``u``:
+    u = ((wv * 6 + ks) * 6 + nb) * 64 + lane   holds   W[32 ks + 8 (lane >> 4) + j][96 wv + 16 nb + (lane & 15)], j = 0..7
+    -- the MFMA operand that lane feeds for column block ``nb`` at k step ``ks`` in wave ``wv``."""
+    u = torch.arange(PACK_ROWS * PACK_W2_N // 8)
+    lane, t = u % 64, u // 64
+    nb, ks, wv = t % 6, (t // 6) % 6, t // 36
+    row = (32 * ks + 8 * (lane // 16))[:, None] + torch.arange(8)
+    col = (96 * wv + 16 * nb + (lane % 16))[:, None].expand(-1, 8)
+    return torch.stack([row, col], dim=2)
+
+
+def pack_weight_frags_w2_ref(W):
+    """``pack_index_w2`` applied with torch indexing (any device): the definition ``pack_weight_frags_w2`` is tested against."""
+    assert tuple(W.shape) == (PACK_ROWS, PACK_W2_N)
+    idx = pack_index_w2().to(W.device)
+    return W[idx[..., 0], idx[..., 1]].reshape(PACK_ROWS, PACK_W2_N)
+
+
+def pack_weight_frags_w2(srcs, dsts):
+    """dsts[j] = ``pack_index_w2`` copy of srcs[j] ((192, 384) bf16 contiguous), one launch per 64 weights
+    (fv_pack_weight_frags_w2_batched)."""
+    lib = L.lib()
+    for lo in range(0, len(srcs), 64):
+        a, b = srcs[lo:lo + 64], dsts[lo:lo + 64]
+        assert all(t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (PACK_ROWS, PACK_W2_N) for t in a)
+        assert all(t.dtype == torch.bfloat16 and t.is_contiguous() and t.numel() == PACK_ROWS * PACK_W2_N for t in b)
+        k = len(a)
+        ins = (ctypes.c_void_p * k)(*[t.data_ptr() for t in a])
+        outs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in b])
+        L.check(lib.fv_pack_weight_frags_w2_batched(ins, outs, L.i32(k), L.stream_of(a[0])), "pack_weight_frags_w2_batched")
 
 
 XPROJ_WIDTHS = (44, 56, 80, 96, 112, 34, 36, 38, 64)

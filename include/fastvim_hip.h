@@ -47,6 +47,9 @@ const char* fv_last_error(void);
  *      Later, still 3: fv_pack_weight_frags_batched, fv_mixer_conv_pool_bwd_dgrad_pk and
  *      fv_mixer_combine_out_proj_addnorm_pk were ADDED (projection weights streamed in MFMA fragment order); the plain
  *      entry points keep their signatures and the plain layout.
+ *      Later, still 3: fv_pack_weight_frags_w2_batched and fv_mixer_conv_pool_bwd_dgrad_pk2 were ADDED (the second
+ *      weight of the fused backward launch streamed in MFMA fragment order); no existing entry point changed --
+ *      fv_pack_weight_frags_batched keeps the meaning of K and its checks.
  *      Later, still 3: fv_mix_batch, fv_patch_unfold_mix, fv_mixup_target and fv_label_ce were ADDED (batch Mixup /
  *      CutMix and the losses on integer labels).
  *      Later, still 3: fv_patch_unfold_chan, fv_chan_embed_table and fv_chan_embed_scatter were ADDED (hierarchical
@@ -530,6 +533,19 @@ int fv_mixer_conv_pool_bwd_dgrad_pk(const void* xz, const void* dskip, const flo
                                     const float* norm_weight, const float* row_scale, int rows_per_scale, void* dx,
                                     float* dresidual_in, float* partial_dw, const void* W2, void* C2, int N2, long ldw2,
                                     fv_stream_t stream);
+/* ... and with W2 given as the FRAGMENT-MAJOR copy of the previous block's out_proj.weight for the product in which its
+ * rows are k (fv_pack_weight_frags_w2_batched).  W2 and C2 not null, N2 == 384, ldw2 == 384 (no row padding).  The second
+ * phase then streams W2 from L2 into MFMA operand registers, each wave for 96 columns of C2 and all 64 tile rows; same
+ * operands, k order and accumulation chains: every output is bit-identical to the two launches above. */
+int fv_mixer_conv_pool_bwd_dgrad_pk2(const void* xz, const void* dskip, const float* dxc, const void* dxc2,
+                                     const float* conv_w, const float* conv_b, const float* conv_w_b,
+                                     const float* conv_b_b, const float* D, const float* D_b, void* dxz,
+                                     float* conv_partials, int batch, int rows, int cols, int tok_stride_row,
+                                     int tok_stride_col, float scaling, const void* W_in_t, long ldwt,
+                                     const float* dresidual_out, const float* r, const float* rstd,
+                                     const float* norm_weight, const float* row_scale, int rows_per_scale, void* dx,
+                                     float* dresidual_in, float* partial_dw, const void* W2, void* C2, int N2, long ldw2,
+                                     fv_stream_t stream);
 
 /* dsts[j] (cols, rows) bf16 = srcs[j] (rows, cols)^T for up to 64 equal-shape matrices in one launch: the transposed
  * bf16 shadows of in_proj.weight that fv_mixer_conv_pool_bwd_dgrad reads (refreshed once per optimizer step). */
@@ -542,6 +558,13 @@ int fv_transpose_bf16_batched(const void* const* srcs, void* const* dsts, int nj
  * (wv 0..3, ks 0..K/32-1, nb 0..2, lane 0..63) -- the MFMA operand lane `lane` of wave wv loads for column block nb at
  * k step ks in the _pk launches above.  Both sides 16-byte aligned, no aliasing.  Refreshed once per optimizer step. */
 int fv_pack_weight_frags_batched(const void* const* srcs, void* const* dsts, int njobs, int K, fv_stream_t stream);
+
+/* Fragment-major copies of up to 64 weights (192, 384) bf16 row-major whose ROWS are k (out_proj.weight as the operand of
+ * its data gradient), in one launch; dsts[j] holds the same elements in 16-byte units:
+ *   unit ((wv * 6 + ks) * 6 + nb) * 64 + lane  =  srcs[j][32 ks + 8 (lane >> 4) + j'][96 wv + 16 nb + (lane & 15)], j' = 0..7
+ * (wv 0..3, ks 0..5, nb 0..5, lane 0..63) -- the MFMA operand lane `lane` of wave wv feeds for column block nb at k step
+ * ks in the second phase of fv_mixer_conv_pool_bwd_dgrad_pk2.  dsts 16-byte aligned, no aliasing. */
+int fv_pack_weight_frags_w2_batched(const void* const* srcs, void* const* dsts, int njobs, fv_stream_t stream);
 
 /* fv_gemm_bf16_addnorm with a second GEMM phase: C2 (M, N2) bf16 = y @ W2^T, W2 (N2, N) bf16 row-major -- the block's
  * in_proj (mamba_simple_faster.py:189-193) computed from the normalised tile while it is still in LDS; bit-identical to
