@@ -603,6 +603,21 @@ class FlatAdamW:
             raise RuntimeError("FlatAdamW was built without ema_decay")
         return {prefix + n: v.detach().clone() for n, v in self._named_slices(self.ema).items()}
 
+    def swap_ema_(self):
+        """Exchange the live weights and the EMA weights in place: ONE launch (csrc/eval.hip, ``fv_swap_params_ema``) swaps
+        ``param_flat`` and ``ema`` bit for bit and re-casts ``shadow_flat`` from the new ``param_flat``; then every derived
+        copy ``step()`` re-makes is re-made (``refresh_transposed``).  The model now computes with the EMA weights; a
+        second call restores all of it bit for bit (``fastvim_amd.evaluate.ema_weights`` is the context manager).
+        Capturable, and like ``step()`` it bumps no ``_version``: the kernel itself leaves the shadow consistent."""
+        if self.ema is None:
+            raise RuntimeError("FlatAdamW was built without ema_decay: there are no EMA weights to swap in")
+        f = self.flat
+        rc = L.lib().fv_swap_params_ema(L.ptr(f.param_flat), L.ptr(self.ema), L.ptr(f.shadow_flat),
+                                        L.i32(L.dtype_code(f.shadow_flat.dtype)), ctypes.c_size_t(f.param_flat.numel()),
+                                        L.stream_of(f.param_flat))
+        L.check(rc, "swap_params_ema")
+        f.refresh_transposed()
+
     def step(self, grad_scale=1.0):
         """``grad_scale``: factor applied to every gradient element as it is read (``1 / world_size`` after an
         ``allreduce_sum_`` / ``GradExchange.finish(mean=False)``: the data-parallel mean without its own pass)."""

@@ -64,7 +64,9 @@ const char* fv_last_error(void);
  *      there is one patch column (the un-pooled geometry of the masked MAE encoders and the Vim mixer).
  *      Later, still 3: fv_bn1d_stats, fv_bn1d_apply, fv_bn1d_bwd, fv_sgd_flat, fv_lars_partials_per_segment,
  *      fv_lars_sumsq_partials and fv_lars_flat were ADDED (the linear-probe recipe: BatchNorm1d over pooled features,
- *      momentum SGD and LARS over the flat buffers). */
+ *      momentum SGD and LARS over the flat buffers).
+ *      Later, still 3: fv_swap_params_ema and fv_eval_accumulate were ADDED (the validation step: the batch under the
+ *      live and the EMA weights, metrics accumulated on the device). */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -843,6 +845,43 @@ int fv_lars_sumsq_partials(const float* params, const float* grads, const int64_
 int fv_lars_flat(float* params, const float* grads, float* momentum_buf, void* shadow_bf16, const int64_t* segments,
                  int n_segments, const float* partials, const float* lr, float* norms, float momentum,
                  float weight_decay, float trust_coefficient, float grad_scale, size_t n, fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * The validation step of the reference's supervised loops (imagenet_classification/supervised_imagenet.py:151-210,
+ * mae/finetune_imagenet.py:165-221, cell_imaging/supervised.py:132-165): every batch through the live backbone and
+ * through the EMA copy, loss and top-1 accuracy of each as epoch means.
+ *
+ * fv_swap_params_ema: ONE pass that exchanges params[i] and ema[i] (fp32, bit for bit, NaN payloads included) and writes
+ *   shadow[i] = cast(new params[i]) in shadow_dtype (FV_BF16, FV_F16: round to nearest even, denormals kept, a NaN stays
+ *   a NaN; FV_F32: a copy) -- the flat training state's weights become the EMA weights in place, and a second call puts
+ *   all three buffers back.  No arithmetic on the values.  8 B read and 8 B + the shadow element written per element (18 B with bf16).
+ *   n is arbitrary; the buffers need only the alignment of their element type: 16-byte accesses are used from the first
+ *   element at which params, ema and the shadow are all aligned for them (the start of equally offset views of aligned
+ *   allocations), single elements before it, for the tail, and throughout when no such element exists.
+ *
+ * fv_eval_accumulate: two launches that add one batch to an accumulator block.
+ *   logits (batch, classes) fp32 or bf16; labels (batch,) int64; classes <= 2048
+ *   n_valid      one int32 in DEVICE memory, read when the kernels run (a captured launch sees what the host wrote
+ *                before the replay): only rows b < min(max(*n_valid, 0), batch) count.  The other rows' logits and
+ *                labels are not read, whatever they hold.
+ *   loss_rows, correct_rows   scratch, (batch,) fp32 / int32: for a counted row exactly what fv_label_ce(mix = NULL,
+ *                smoothing = 0) writes there (same row body, bit-identical), for the other rows 0
+ *   acc          the accumulator block, FV_EVAL_ACC_HEAD + 2 * classes 64-bit words, 8-byte aligned, zeroed by the caller
+ *                at the start of an epoch:
+ *                  word 0                       loss_sum, an fp64: += the sum of the counted rows' fp32 losses, taken in
+ *                                               fp64 in one fixed order (no float atomics)
+ *                  word 1                       n_seen, int64: += the number of counted rows
+ *                  word 2                       n_correct, int64: += the counted rows whose arg-max is their label
+ *                  words 3 .. 3 + classes       support[c], int64: += the counted rows with label c
+ *                  words 3 + classes .. end     hit[c], int64: += those of them that are correct
+ *                A counted row whose label is outside [0, classes) adds to n_seen only (its loss is 0, it is never correct
+ *                and belongs to no class); no label value causes an access outside the block.  The same batches in the
+ *                same order leave the same bytes.
+ * ---------------------------------------------------------------------- */
+#define FV_EVAL_ACC_HEAD 3
+int fv_swap_params_ema(float* params, float* ema, void* shadow, int shadow_dtype, size_t n, fv_stream_t stream);
+int fv_eval_accumulate(const void* logits, int logits_dtype, const int64_t* labels, const int32_t* n_valid,
+                       float* loss_rows, int32_t* correct_rows, int64_t* acc, int batch, int classes, fv_stream_t stream);
 
 #ifdef __cplusplus
 }
