@@ -37,6 +37,7 @@ C_ABI_SYMBOLS = (
     "fv_bn1d_stats", "fv_bn1d_apply", "fv_bn1d_bwd", "fv_sgd_flat", "fv_lars_partials_per_segment", "fv_lars_sumsq_partials", "fv_lars_flat",
     "fv_tap_ln_blocks", "fv_tap_ln_fwd", "fv_tap_ln_bwd", "fv_ln2d_blocks", "fv_ln2d_fwd", "fv_ln2d_bwd",
     "fv_swap_params_ema", "fv_eval_accumulate",
+    "fv_patch_unfold_u8", "fv_patch_unfold_mix_u8", "fv_patch_unfold_chan_u8",
 )
 
 

@@ -99,6 +99,73 @@ def patch_unfold_mix(x, ph, pw, out_dtype, block):
     return out
 
 
+# ---- 8-bit images: the unfolds above with the per-channel normalisation as a table lookup (csrc/unfold_u8.hip) ----------
+# ``table``: the (C, 256) fp32 tensor of fastvim_amd.pixels.PixelNorm.table(device).  Each function is bit for bit the float
+# function of the same name applied to ``table[c][x]`` as an fp32 image; the ``_u8_ok`` predicates are pure host functions
+# of the tensor's shape, dtype, layout and address (a meta or CPU stand-in answers for the shape).
+
+def _u8_images(x, align):
+    # (is_cuda is the caller's check: the kernels run on the GPU only, the predicate also answers for a stand-in)
+    return (x.dim() == 4 and x.dtype == torch.uint8 and x.is_contiguous()
+            and (x.device.type == "meta" or x.data_ptr() % align == 0))
+
+
+def patch_unfold_u8_ok(x, ph, pw):
+    """Any even patch width from 8 up, 16 fp32 patches plus the table (1 KB per channel) within 64 KB of LDS, NCHW-contiguous
+    images at an even address (16 pixels per load where width and address allow, down to 2)."""
+    return (_u8_images(x, 2) and pw % 2 == 0 and pw >= 8 and x.shape[2] % ph == 0 and x.shape[3] % pw == 0
+            and x.shape[1] * (ph * pw * 16 * 4 + 1024) <= 64 * 1024)
+
+
+def patch_unfold_chan_u8_ok(x, ph, pw, n_sel):
+    return (_u8_images(x, 4) and pw % 8 == 0 and x.shape[2] % ph == 0 and x.shape[3] % pw == 0
+            and 0 < n_sel <= x.shape[1] and n_sel * (ph * pw * 4 + 1024) <= 64 * 1024)
+
+
+def _u8_table(x, table, rows):
+    L.require_gpu(x, table)
+    if table.dtype != torch.float32 or tuple(table.shape) != (rows, 256) or not table.is_contiguous() or table.device != x.device:
+        raise RuntimeError(f"pixel table: expected a contiguous fp32 ({rows}, 256) tensor on {x.device}, got "
+                           f"{tuple(table.shape)} {table.dtype} on {table.device}")
+
+
+def patch_unfold_u8(x, table, ph, pw, out_dtype):
+    """uint8 (B, C, H, W) -> (B, gh*gw, C*ph*pw) in ``out_dtype``: ``patch_unfold(table[c][x], ph, pw, out_dtype)`` in one
+    launch that reads a quarter of the image bytes."""
+    B, C, H, W = x.shape
+    _u8_table(x, table, C)
+    out = torch.empty(B, (H // ph) * (W // pw), C * ph * pw, device=x.device, dtype=out_dtype)
+    rc = L.lib().fv_patch_unfold_u8(L.ptr(x), L.ptr(table), L.ptr(out), L.i32(L.dtype_code(out_dtype)), L.i32(B), L.i32(C),
+                                    L.i32(H), L.i32(W), L.i32(ph), L.i32(pw), L.stream_of(x))
+    L.check(rc, "patch_unfold_u8")
+    return out
+
+
+def patch_unfold_mix_u8(x, table, ph, pw, out_dtype, block):
+    """``patch_unfold_mix(table[c][x], ph, pw, out_dtype, block)``: the pixels are looked up, then mixed in fp32 with the
+    float kernel's expressions.  Applicable where ``patch_unfold_u8_ok`` and the batch is even."""
+    B, C, H, W = x.shape
+    _u8_table(x, table, C)
+    out = torch.empty(B, (H // ph) * (W // pw), C * ph * pw, device=x.device, dtype=out_dtype)
+    rc = L.lib().fv_patch_unfold_mix_u8(L.ptr(x), L.ptr(table), L.ptr(out), L.i32(L.dtype_code(out_dtype)), L.i32(B), L.i32(C),
+                                        L.i32(H), L.i32(W), L.i32(ph), L.i32(pw), L.ptr(block), L.stream_of(x))
+    L.check(rc, "patch_unfold_mix_u8")
+    return out
+
+
+def patch_unfold_chan_u8(x, table, ph, pw, out_dtype, sel, n_sel, colwise=False):
+    """``patch_unfold_chan(table[c][x], ...)``: output channel k is looked up in row ``sel[k]`` of the table -- the SOURCE
+    channel's statistics (``sel`` None: row k)."""
+    B, Ctot, H, W = x.shape
+    _u8_table(x, table, Ctot)
+    out = torch.empty(B, (H // ph) * (W // pw) * n_sel, ph * pw, device=x.device, dtype=out_dtype)
+    rc = L.lib().fv_patch_unfold_chan_u8(L.ptr(x), L.ptr(table), L.ptr(out), L.i32(L.dtype_code(out_dtype)), L.i32(B), L.i32(Ctot),
+                                         L.i32(H), L.i32(W), L.i32(ph), L.i32(pw), L.ptr(sel), L.i32(n_sel),
+                                         L.i32(bool(colwise)), L.stream_of(x))
+    L.check(rc, "patch_unfold_chan_u8")
+    return out
+
+
 def gemm_rowbias(a, w, table):
     """fp32 (M, N) = bf16_round(a (M, K) @ w (N, K)^T) + table[m mod period]: bf16 operands, table (period, N) fp32."""
     M, K = a.shape

@@ -21,6 +21,7 @@ from torch import Tensor
 from .fastvim import (DropPath, _compute_dtype, _init_weights, segm_init_weights as _segm_2d,
                       to_2tuple, trunc_normal_)
 from . import glue_ops as G
+from . import pixels
 from .hcs import draw as draw_channels, upload as upload_channels
 from .layernorm import RMSNorm, layer_norm_fn
 from .mamba_simple_channel_faster import Mamba
@@ -172,12 +173,22 @@ class PatchEmbedPerChannel(nn.Module):
         ph, pw = self.patch_size
         gh, gw = h // ph, w // pw
         g0, g1 = (gw, gh) if self.scanpath_type == "colwise" else (gh, gw)       # :193-194
-        cdt = _compute_dtype(x)
+        table = None
+        if x.dtype == torch.uint8:
+            # 8-bit images (fastvim_amd/pixels.py): looked up in row sel[k] -- the SOURCE channel's -- of the attached table
+            # inside the unfold launch; where that kernel does not apply, the eager lookup and then everything below as for
+            # float images (same values)
+            table = pixels.pixel_table(self, x)
+            if not (x.is_cuda and input_channel_order is None and G.patch_unfold_chan_u8_ok(x, ph, pw, num_channels)
+                    and _compute_dtype(table) in (torch.float32, torch.bfloat16)
+                    and num_channels <= self.channel_embed.weight.shape[0]):
+                x, table = pixels.lookup(table, x), None
+        cdt = _compute_dtype(x if table is None else table)      # (uint8: the autocast dtype, fp32 outside autocast)
         D = self.proj.weight.shape[0]
         # the HIP embed: gather + unfold + cast in one launch, the per-token table, the GEMM.  Per-sample channel ids, an
         # image that asks for its gradient (the unfold has no autograd node), CPU tensors and shapes outside the unfold's
         # limits keep the strided-copy chain below
-        kernels = (input_channel_order is None and G.patch_unfold_chan_ok(x, ph, pw, num_channels)
+        kernels = (input_channel_order is None and (table is not None or G.patch_unfold_chan_ok(x, ph, pw, num_channels))
                    and cdt in (torch.float32, torch.bfloat16) and not (x.requires_grad and torch.is_grad_enabled())
                    and num_channels <= self.channel_embed.weight.shape[0])
         sel = None
@@ -201,7 +212,10 @@ class PatchEmbedPerChannel(nn.Module):
             sampled = False
         C = len(channels)
         if kernels:
-            patches = G.patch_unfold_chan(x, ph, pw, cdt, sel, C, colwise=self.scanpath_type == "colwise")
+            if table is None:
+                patches = G.patch_unfold_chan(x, ph, pw, cdt, sel, C, colwise=self.scanpath_type == "colwise")
+            else:
+                patches = G.patch_unfold_chan_u8(x, table, ph, pw, cdt, sel, C, colwise=self.scanpath_type == "colwise")
             out = _ChanPatchProjFn.apply(patches, self.proj.weight, self.proj.bias, self.channel_embed.weight, pos_embed,
                                          sel, C, cdt).view(B, g0 * g1, C, D)
         else:

@@ -276,6 +276,11 @@ class MaskedAutoencoderViM(nn.Module):
         return (loss * mask).sum() / mask.sum()
 
     def forward(self, imgs, mask_ratio=0.75, inference_params=None, noise=None):
+        """``imgs``: normalised float images.  uint8 batches (fastvim_amd/pixels.py) are out of scope here: the loss
+        patchifies the float image."""
+        if imgs.dtype == torch.uint8:
+            raise TypeError("MaskedAutoencoderViM: uint8 images are not supported (the reconstruction loss patchifies the "
+                            "normalised float image); normalise the batch first, e.g. with fastvim_amd.pixels.PixelNorm")
         latent, mask, ids_restore = self.forward_encoder(imgs, mask_ratio, inference_params, noise=noise)
         pred = self.forward_decoder(latent, ids_restore, inference_params)
         loss = self.forward_loss(imgs, pred, mask)

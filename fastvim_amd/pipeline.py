@@ -23,11 +23,14 @@ import warnings
 import torch
 import torch.distributed as dist
 
+from . import pixels
+
 
 class SegmentedTrainStep:
     """``model`` must expose ``_embed / _run_layers / _final / _head`` (fastvim_amd.fastvim.VisionMamba).
     ``loss_fn(logits, target) -> scalar``.  ``x`` / ``target`` are the static input buffers the graphs read; copy
-    new batches into them between steps.
+    new batches into them between steps.  ``x`` holds normalised float pixels, or -- after
+    ``fastvim_amd.pixels.attach_pixel_norm(model, mean, std)`` -- the uint8 batch itself, normalised inside the patch unfold.
 
     ``mixup`` (a ``fastvim_amd.mixup.Mixup``, with ``loss_fn = mixup.criterion()`` and ``target`` the (B,) int64 labels):
     the batch is mixed inside the step with the parameters of the last ``mixup.sample()``, which the caller issues between
@@ -58,7 +61,10 @@ class SegmentedTrainStep:
             mixup.bind(x)                                # image size for the boxes; the block exists before any capture
             self._embed_takes_mix = "mix" in inspect.signature(model._embed).parameters
             if not self._embed_takes_mix:                # such a model gets the mixed batch from one fv_mix_batch launch
-                self._x_mixed = torch.empty_like(x, memory_format=torch.contiguous_format)
+                # (a uint8 `x` -- fastvim_amd/pixels.py -- is normalised by the eager table lookup first and mixed after it, in
+                # fp32: the mixed batch is a float buffer, what the embed would have been handed by a host-side loader)
+                self._x_mixed = torch.empty_like(x, memory_format=torch.contiguous_format,
+                                                 dtype=torch.float32 if x.dtype == torch.uint8 else x.dtype)
         # hierarchical channel sampling: the subset of the sampler's device array, one family of graphs per channel count
         self.hcs = hcs
         if hcs is not None and "hcs" not in inspect.signature(model._embed).parameters:
@@ -98,7 +104,8 @@ class SegmentedTrainStep:
             elif self._embed_takes_mix:
                 h, _ = m._embed(self.x, mix=self.mixup, **kw)
             else:              # (the channel models: the whole image is mixed before channels are selected, the reference's order)
-                h, _ = m._embed(self.mixup.mix_batch(self.x, out=self._x_mixed), **kw)
+                xin = pixels.normalise_like(m, self.x) if self.x.dtype == torch.uint8 else self.x
+                h, _ = m._embed(self.mixup.mix_batch(xin, out=self._x_mixed), **kw)
             res, pend = None, None
             fwd_runs = self.runs[::-1]
             open_runs = hasattr(m, "_run_layers_open")

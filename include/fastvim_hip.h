@@ -66,7 +66,9 @@ const char* fv_last_error(void);
  *      fv_lars_sumsq_partials and fv_lars_flat were ADDED (the linear-probe recipe: BatchNorm1d over pooled features,
  *      momentum SGD and LARS over the flat buffers).
  *      Later, still 3: fv_swap_params_ema and fv_eval_accumulate were ADDED (the validation step: the batch under the
- *      live and the EMA weights, metrics accumulated on the device). */
+ *      live and the EMA weights, metrics accumulated on the device).
+ *      Later, still 3: fv_patch_unfold_u8, fv_patch_unfold_mix_u8 and fv_patch_unfold_chan_u8 were ADDED (8-bit image
+ *      batches: the per-channel normalisation as a table lookup inside the patch unfold). */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -749,6 +751,29 @@ int fv_chan_embed_table(const float* chan_table, const float* bias, const float*
  * fp32.  The rows of channels that were not drawn are not touched.  One thread owns an element: no atomics. */
 int fv_chan_embed_scatter(const float* d_chan, float* d_table, const int32_t* sel, int n_sel, int chans_total, int dim,
                           fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * 8-bit images: the three patch unfolds above with the loader's per-channel normalisation (ToTensor + Normalize,
+ * A.Normalize) as a table lookup.  img is uint8, (batch, chans, height, width) contiguous; table is fp32
+ * (chans, 256) in device memory, read when the kernel runs, built by the HOST in the loader's own order of operations
+ * (fastvim_amd/pixels.py) -- the kernels do no arithmetic on a pixel that a fast-math build could rewrite.  A pixel
+ * becomes table[c][img] (c the SOURCE channel: sel[k] in the per-channel form) and from there on is treated exactly
+ * as the float entry points treat an fp32 image, so for out_dtype fp32 and bf16
+ *   fv_patch_unfold_u8(img, table)      == fv_patch_unfold(table[c][img] as an fp32 image)
+ *   fv_patch_unfold_mix_u8(img, table)  == fv_patch_unfold_mix(...)   (mixed in fp32, products rounded separately)
+ *   fv_patch_unfold_chan_u8(img, table) == fv_patch_unfold_chan(...)  (an index outside [0, chans_total) is clamped)
+ * bit for bit.  Output layouts, sel / mix blocks and the limits on the patch shape are those of the float entry
+ * points, with the table (1 KB per channel) sharing the workgroup's 64 KB of LDS with the staging tile.  Image rows
+ * are loaded 16 bytes at a time where width, patch width and the image's base address allow, else 8, 4 or 2: the image
+ * must be 2-byte aligned (4-byte for the per-channel form), table and out 16-byte aligned.
+ * ---------------------------------------------------------------------- */
+int fv_patch_unfold_u8(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans,
+                       int height, int width, int ph, int pw, fv_stream_t stream);
+int fv_patch_unfold_mix_u8(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans,
+                           int height, int width, int ph, int pw, const void* mix, fv_stream_t stream);
+int fv_patch_unfold_chan_u8(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans_total,
+                            int height, int width, int ph, int pw, const int32_t* sel, int n_sel, int colwise,
+                            fv_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Fused AdamW (decoupled weight decay, bias correction; torch.optim.AdamW semantics) over a flat fp32
