@@ -38,6 +38,7 @@ C_ABI_SYMBOLS = (
     "fv_tap_ln_blocks", "fv_tap_ln_fwd", "fv_tap_ln_bwd", "fv_ln2d_blocks", "fv_ln2d_fwd", "fv_ln2d_bwd",
     "fv_swap_params_ema", "fv_eval_accumulate",
     "fv_patch_unfold_u8", "fv_patch_unfold_mix_u8", "fv_patch_unfold_chan_u8",
+    "fv_random_erase", "fv_patch_unfold_u8_re", "fv_patch_unfold_mix_u8_re",
 )
 
 

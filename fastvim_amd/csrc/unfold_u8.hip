@@ -18,7 +18,13 @@
 //
 // The small helpers below (element stores, round_as, the mixing expressions, the channel clamp) restate those of glue.hip,
 // which this change leaves untouched; tests/test_unfold_u8_gpu.py holds the two files to bit equality.
+//
+// Random erasing (the _re entry points): ERASE = true forms of the plain and the pair kernel replace, between the lookup
+// and the placement / the mixing, the pixels inside the sample's box by 0 or by the noise of erase_noise.h -- what
+// fv_random_erase writes into the normalised fp32 image, bit for bit.  The ERASE = false forms are the code they were,
+// but for the box test of mix_pixels_f32.
 #include "common.h"
+#include "erase_noise.h"
 
 namespace {
 
@@ -101,10 +107,10 @@ __device__ __forceinline__ void stage_table(float* tab, const float* __restrict_
 }
 
 // ---- plain: out[b][gi*gw + gj][(c*ph + pi)*pw + pj] = table[c][img[b][c][gi*ph + pi][gj*pw + pj]] ---------------------
-template <typename TO, int LV, int PV>
+template <typename TO, int LV, int PV, bool ERASE>
 __global__ __launch_bounds__(256) void patch_unfold_u8_kernel(const uint8_t* __restrict__ img, const float* __restrict__ table,
                                                               TO* __restrict__ out, int C, int H, int W, int ph, int pw, int gw,
-                                                              int sw, int tile_bytes) {
+                                                              int sw, int tile_bytes, const int32_t* __restrict__ erase) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   TO* tile = reinterpret_cast<TO*>(smem);
   float* tab = reinterpret_cast<float*>(smem + tile_bytes);
@@ -115,11 +121,18 @@ __global__ __launch_bounds__(256) void patch_unfold_u8_kernel(const uint8_t* __r
   const int Kp = C * ph * pw;                 // elements per patch row
   const int xv = gjn * pw / LV;               // LV-pixel vectors per image-row segment of the chunk
   const uint8_t* src = img + ((size_t)b * C * H + (size_t)gi * ph) * W + (size_t)gj0 * pw;
+  fv_erase::Key ek = {};
+  fv_erase::Box eb = {};
+  if constexpr (ERASE) {
+    ek = fv_erase::load_key(erase);
+    eb = fv_erase::load_box(erase, b);
+  }
   for (int e = threadIdx.x; e < C * ph * xv; e += blockDim.x) {
     const int row = e / xv, x = (e - row * xv) * LV;     // row = c * ph + pi
     const int c = row / ph, pi = row - c * ph;
     float v[LV];
     lookup_row<LV>(src + ((size_t)c * H + pi) * W + x, tab + c * 256, v);
+    if constexpr (ERASE) fv_erase::erase_segment<LV>(ek, eb, b, c, gi * ph + pi, gj0 * pw + x, v);      // (gj0 * pw % 16 == 0)
     place_row<TO, LV, PV>(tile, Kp, pw, row, x, v);
   }
   __syncthreads();
@@ -191,21 +204,23 @@ __device__ __forceinline__ void mix_pixels_f32(const fv_mix_params& P, int mode,
       op[k] = round_f32(round_f32(p[k] * P.lam) + round_f32(a[k] * P.one_minus_lam));
     }
   } else {
-    const bool in_rows = mode == U8_MIX_CUTMIX && y >= P.yl && y < P.yh;
+    // (plain & on the flags, no short-circuit: with `&&` the compiler turned the row test into a branch around the selects
+    // and, in the 2-pixel form, left element 0 of rows outside the box unwritten -- tests/test_erasing_gpu.py, the LV 2 case)
+    const bool in_rows = (mode == U8_MIX_CUTMIX) & (y >= P.yl) & (y < P.yh);
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-      const bool in_box = in_rows && x0 + k >= P.xl && x0 + k < P.xh;
+      const bool in_box = in_rows & (x0 + k >= P.xl) & (x0 + k < P.xh);
       oa[k] = in_box ? p[k] : a[k];
       op[k] = in_box ? a[k] : p[k];
     }
   }
 }
 
-template <typename TO, int LV, int PV>
+template <typename TO, int LV, int PV, bool ERASE>
 __global__ __launch_bounds__(U8_MIX_THREADS) void patch_unfold_mix_u8_kernel(const uint8_t* __restrict__ img, const float* __restrict__ table,
                                                                             TO* __restrict__ out, const fv_mix_params* __restrict__ mp,
                                                                             int B, int C, int H, int W, int ph, int pw, int gw, int sw,
-                                                                            int tile_bytes) {
+                                                                            int tile_bytes, const int32_t* __restrict__ erase) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const fv_mix_params P = *mp;
   const int mode = P.use_cutmix ? U8_MIX_CUTMIX : (P.lam == 1.f ? U8_MIX_COPY : U8_MIX_MIXUP);
@@ -221,6 +236,13 @@ __global__ __launch_bounds__(U8_MIX_THREADS) void patch_unfold_mix_u8_kernel(con
   const size_t org = (size_t)gi * ph * W + (size_t)gj0 * pw;
   const uint8_t* src_a = img + (size_t)ba * C * H * W + org;
   const uint8_t* src_p = img + (size_t)bp * C * H * W + org;
+  fv_erase::Key ek = {};
+  fv_erase::Box eba = {}, ebp = {};
+  if constexpr (ERASE) {      // each image of the pair is erased with its own box, then the two are mixed
+    ek = fv_erase::load_key(erase);
+    eba = fv_erase::load_box(erase, ba);
+    ebp = fv_erase::load_box(erase, bp);
+  }
   for (int e = threadIdx.x; e < C * ph * xv; e += blockDim.x) {
     const int row = e / xv, x = (e - row * xv) * LV;     // row = c * ph + pi
     const int c = row / ph, pi = row - c * ph;
@@ -228,6 +250,10 @@ __global__ __launch_bounds__(U8_MIX_THREADS) void patch_unfold_mix_u8_kernel(con
     float a[LV], p[LV], ra[LV], rp[LV];
     lookup_row<LV>(src_a + off, tab + c * 256, a);
     lookup_row<LV>(src_p + off, tab + c * 256, p);
+    if constexpr (ERASE) {
+      fv_erase::erase_segment<LV>(ek, eba, ba, c, gi * ph + pi, gj0 * pw + x, a);
+      fv_erase::erase_segment<LV>(ek, ebp, bp, c, gi * ph + pi, gj0 * pw + x, p);
+    }
     mix_pixels_f32<LV>(P, mode, gi * ph + pi, gj0 * pw + x, a, p, ra, rp);
     place_row<TO, LV, PV>(tile_a, Kp, pw, row, x, ra);
     place_row<TO, LV, PV>(tile_p, Kp, pw, row, x, rp);
@@ -261,16 +287,23 @@ bool out_dt_ok(int dt) { return dt == FV_F32 || dt == FV_BF16; }
 }  // namespace
 
 // one of the (LV, PV) forms of a plain / pair kernel: PV = 4 where the patch width is a multiple of 4, else pairs
-#define FV_U8_FORMS(LAUNCH, TO)                                   \
+#define FV_U8_FORMS(LAUNCH, TO, RE)                               \
   do {                                                            \
-    if (lv == 16) { if (pv4) LAUNCH(TO, 16, 4); else LAUNCH(TO, 16, 2); } \
-    else if (lv == 8) { if (pv4) LAUNCH(TO, 8, 4); else LAUNCH(TO, 8, 2); } \
-    else if (lv == 4) { if (pv4) LAUNCH(TO, 4, 4); else LAUNCH(TO, 4, 2); } \
-    else LAUNCH(TO, 2, 2);                                        \
+    if (lv == 16) { if (pv4) LAUNCH(TO, 16, 4, RE); else LAUNCH(TO, 16, 2, RE); } \
+    else if (lv == 8) { if (pv4) LAUNCH(TO, 8, 4, RE); else LAUNCH(TO, 8, 2, RE); } \
+    else if (lv == 4) { if (pv4) LAUNCH(TO, 4, 4, RE); else LAUNCH(TO, 4, 2, RE); } \
+    else LAUNCH(TO, 2, 2, RE);                                    \
+  } while (0)
+// the plain / the _re entry point: the same launch with ERASE false / true
+#define FV_U8_DTYPES(LAUNCH)                                      \
+  do {                                                            \
+    if (erase) { if (out_dtype == FV_BF16) FV_U8_FORMS(LAUNCH, bf16_t, true); else FV_U8_FORMS(LAUNCH, float, true); } \
+    else { if (out_dtype == FV_BF16) FV_U8_FORMS(LAUNCH, bf16_t, false); else FV_U8_FORMS(LAUNCH, float, false); } \
   } while (0)
 
-extern "C" int fv_patch_unfold_u8(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans,
-                                  int height, int width, int ph, int pw, fv_stream_t stream) {
+// erase == nullptr: the plain launch; else the block of the _re entry point
+static int unfold_u8_launch(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans, int height,
+                            int width, int ph, int pw, const int32_t* erase, fv_stream_t stream) {
   FV_CHECK(img && table && out, "patch_unfold_u8: null pointer");
   FV_CHECK(out_dt_ok(out_dtype), "patch_unfold_u8: the output must be fp32 or bf16");
   FV_CHECK(batch > 0 && chans > 0 && ph > 0 && pw > 0 && height >= ph && width >= pw, "patch_unfold_u8: empty dimension");
@@ -288,16 +321,26 @@ extern "C" int fv_patch_unfold_u8(const uint8_t* img, const float* table, void* 
   const int lv = load_bytes(img, width, U8_GJ * pw);
   const bool pv4 = pw % 4 == 0;
   const int sw = store_bytes(gw, U8_GJ, (size_t)chans * ph * pw * osz);
-#define FV_U8_PLAIN(TO, LV, PV) hipLaunchKernelGGL((patch_unfold_u8_kernel<TO, LV, PV>), grid, block, smem, st, img, table, (TO*)out, chans, height, width, ph, pw, gw, sw, (int)tile)
-  if (out_dtype == FV_BF16) FV_U8_FORMS(FV_U8_PLAIN, bf16_t);
-  else FV_U8_FORMS(FV_U8_PLAIN, float);
+#define FV_U8_PLAIN(TO, LV, PV, RE) hipLaunchKernelGGL((patch_unfold_u8_kernel<TO, LV, PV, RE>), grid, block, smem, st, img, table, (TO*)out, chans, height, width, ph, pw, gw, sw, (int)tile, erase)
+  FV_U8_DTYPES(FV_U8_PLAIN);
 #undef FV_U8_PLAIN
   FV_LAUNCH_CHECK();
   return FV_OK;
 }
 
-extern "C" int fv_patch_unfold_mix_u8(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans,
-                                      int height, int width, int ph, int pw, const void* mix, fv_stream_t stream) {
+extern "C" int fv_patch_unfold_u8(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans,
+                                  int height, int width, int ph, int pw, fv_stream_t stream) {
+  return unfold_u8_launch(img, table, out, out_dtype, batch, chans, height, width, ph, pw, nullptr, stream);
+}
+
+extern "C" int fv_patch_unfold_u8_re(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans,
+                                     int height, int width, int ph, int pw, const void* erase, fv_stream_t stream) {
+  FV_CHECK(erase && ((uintptr_t)erase & 15) == 0, "patch_unfold_u8_re: the erase block must be a 16-byte aligned device pointer");
+  return unfold_u8_launch(img, table, out, out_dtype, batch, chans, height, width, ph, pw, (const int32_t*)erase, stream);
+}
+
+static int unfold_mix_u8_launch(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans, int height,
+                                int width, int ph, int pw, const void* mix, const int32_t* erase, fv_stream_t stream) {
   FV_CHECK(img && table && out && mix, "patch_unfold_mix_u8: null pointer");
   FV_CHECK(out_dt_ok(out_dtype), "patch_unfold_mix_u8: the output must be fp32 or bf16");
   FV_CHECK(batch > 0 && chans > 0 && ph > 0 && pw > 0 && height >= ph && width >= pw, "patch_unfold_mix_u8: empty dimension");
@@ -318,12 +361,23 @@ extern "C" int fv_patch_unfold_mix_u8(const uint8_t* img, const float* table, vo
   const int lv = load_bytes(img, width, U8_MIX_GJ * pw);
   const bool pv4 = pw % 4 == 0;
   const int sw = store_bytes(gw, U8_MIX_GJ, (size_t)chans * ph * pw * osz);
-#define FV_U8_MIX(TO, LV, PV) hipLaunchKernelGGL((patch_unfold_mix_u8_kernel<TO, LV, PV>), grid, block, smem, st, img, table, (TO*)out, mp, batch, chans, height, width, ph, pw, gw, sw, (int)tile)
-  if (out_dtype == FV_BF16) FV_U8_FORMS(FV_U8_MIX, bf16_t);
-  else FV_U8_FORMS(FV_U8_MIX, float);
+#define FV_U8_MIX(TO, LV, PV, RE) hipLaunchKernelGGL((patch_unfold_mix_u8_kernel<TO, LV, PV, RE>), grid, block, smem, st, img, table, (TO*)out, mp, batch, chans, height, width, ph, pw, gw, sw, (int)tile, erase)
+  FV_U8_DTYPES(FV_U8_MIX);
 #undef FV_U8_MIX
   FV_LAUNCH_CHECK();
   return FV_OK;
+}
+
+extern "C" int fv_patch_unfold_mix_u8(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans,
+                                      int height, int width, int ph, int pw, const void* mix, fv_stream_t stream) {
+  return unfold_mix_u8_launch(img, table, out, out_dtype, batch, chans, height, width, ph, pw, mix, nullptr, stream);
+}
+
+extern "C" int fv_patch_unfold_mix_u8_re(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans,
+                                         int height, int width, int ph, int pw, const void* mix, const void* erase,
+                                         fv_stream_t stream) {
+  FV_CHECK(erase && ((uintptr_t)erase & 15) == 0, "patch_unfold_mix_u8_re: the erase block must be a 16-byte aligned device pointer");
+  return unfold_mix_u8_launch(img, table, out, out_dtype, batch, chans, height, width, ph, pw, mix, (const int32_t*)erase, stream);
 }
 
 extern "C" int fv_patch_unfold_chan_u8(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans_total,
@@ -362,4 +416,5 @@ extern "C" int fv_patch_unfold_chan_u8(const uint8_t* img, const float* table, v
   FV_LAUNCH_CHECK();
   return FV_OK;
 }
+#undef FV_U8_DTYPES
 #undef FV_U8_FORMS

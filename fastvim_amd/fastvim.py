@@ -210,11 +210,14 @@ class PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size)
         self.norm = norm_layer(embed_dim) if norm_layer else nn.Identity()
 
-    def forward(self, x, pos_embed=None, mix=None):
+    def forward(self, x, pos_embed=None, mix=None, erase=None):
         """``pos_embed`` (1, L, D), optional: added in the same epilogue as the conv bias (only for the
         row-major, flattened token order).  ``mix`` (a ``fastvim_amd.mixup.Mixup``), optional: the batch is embedded as
         mixed by the parameters its device block holds -- inside the unfold kernel where that one applies (the mixed
-        images are never written), else by one ``fv_mix_batch`` launch in front."""
+        images are never written), else by one ``fv_mix_batch`` launch in front.  ``erase`` (a
+        ``fastvim_amd.erasing.RandomErasing``), optional: the normalised pixels inside each sample's current box are
+        replaced before the mixing -- inside the uint8 unfold kernel where that one applies, else by one
+        ``fv_random_erase`` launch into a copy of the batch (``x`` itself is never written)."""
         B, C, H, W = x.shape
         if self.strict_img_size:
             assert H == self.img_size[0], f"Input height ({H}) doesn't match model ({self.img_size[0]})."
@@ -234,12 +237,22 @@ class PatchEmbed(nn.Module):
             cdt = _compute_dtype(table)      # the autocast dtype, fp32 outside autocast (the images' own dtype says nothing)
             if not (x.is_cuda and H % ph == 0 and W % pw == 0 and G.patch_unfold_u8_ok(x, ph, pw)
                     and cdt in (torch.float32, torch.bfloat16)):
-                return self.forward(pixels.lookup(table, x), pos_embed=pos_embed, mix=mix)
-            if mix is not None:
+                return self.forward(pixels.lookup(table, x), pos_embed=pos_embed, mix=mix, erase=erase)
+            if erase is not None:
+                erase._check_batch(x)
+                if mix is not None:
+                    patches = G.patch_unfold_mix_u8_re(x, table, ph, pw, cdt, mix.block(x.device), erase.block(x.device))
+                else:
+                    patches = G.patch_unfold_u8_re(x, table, ph, pw, cdt, erase.block(x.device))
+            elif mix is not None:
                 patches = G.patch_unfold_mix_u8(x, table, ph, pw, cdt, mix.block(x.device))
             else:
                 patches = G.patch_unfold_u8(x, table, ph, pw, cdt)
             return self._project(patches, B, C, H // ph, W // pw, cdt, pos_embed)
+        if erase is not None:
+            if x.requires_grad and torch.is_grad_enabled():
+                raise RuntimeError("PatchEmbed: erase= has no gradient with respect to the images")
+            x = erase.erase(x)                       # out of place: loader order, erased first and mixed afterwards
         if mix is not None:
             mix._check_batch(x)
             if x.requires_grad and torch.is_grad_enabled():
@@ -448,12 +461,13 @@ class VisionMamba(nn.Module):
 
     # forward_features (models/fastvim.py:484-546) in three pieces, so that a training step can be cut into segments of
     # layers (fastvim_amd/pipeline.py: gradient buckets exchanged while the next segment's backward runs)
-    def _embed(self, x, mix=None):
+    def _embed(self, x, mix=None, erase=None):
         """``mix``: a ``fastvim_amd.mixup.Mixup`` whose current parameters mix the batch on its way into the patch
-        embedding (training only: ``eval()`` paths never mix)."""
+        embedding; ``erase``: a ``fastvim_amd.erasing.RandomErasing`` whose current boxes are erased before that (training
+        only: ``eval()`` paths neither mix nor erase)."""
         B, _, H, W = x.shape
         if not self.training:
-            mix = None
+            mix = erase = None
         if self.if_abs_pos_embed:
             H, W = math.ceil(H / self.patch_size), math.ceil(W / self.patch_size)
             hw = (H, W) if self.patch_embed.scanpath_type == "rowwise" else (W, H)
@@ -462,11 +476,11 @@ class VisionMamba(nn.Module):
                 # the model with the target img_size instead
                 raise RuntimeError(f"input grid {H}x{W} differs from the model's {self.token_size}; "
                                    "build VisionMamba with the matching img_size")
-            x = self.patch_embed(x, pos_embed=self.pos_embed, mix=mix)     # x + pos_embed (:500) in the epilogue
+            x = self.patch_embed(x, pos_embed=self.pos_embed, mix=mix, erase=erase)     # x + pos_embed (:500) in the epilogue
             x = self.pos_drop(x)
         else:
             H, W = math.ceil(H / self.patch_size), math.ceil(W / self.patch_size)
-            x = self.patch_embed(x, mix=mix)
+            x = self.patch_embed(x, mix=mix, erase=erase)
         if self.training:
             DropPath.predraw([l.drop_path for l in self.layers] + [self.drop_path], x.shape[0], x.device)
         return x, (H, W)

@@ -166,6 +166,68 @@ def patch_unfold_chan_u8(x, table, ph, pw, out_dtype, sel, n_sel, colwise=False)
     return out
 
 
+# ---- random erasing (csrc/erase.hip, the ERASE forms of csrc/unfold_u8.hip) ----------------------------------------------
+# ``block``: the int32 erase block of fastvim_amd.erasing.RandomErasing.block(device) -- boxes, mode and noise key, read when
+# the kernel runs.
+
+def _erase_block(x, block):
+    L.require_gpu(x, block)
+    if (block.dtype != torch.int32 or block.dim() != 1 or not block.is_contiguous() or block.device != x.device
+            or block.numel() < 4 + 4 * x.shape[0] or block.data_ptr() % 16 != 0):
+        raise RuntimeError(f"erase block: expected a contiguous, 16-byte aligned int32 tensor of at least 4 + 4 * {x.shape[0]} "
+                           f"entries on {x.device}, got {tuple(block.shape)} {block.dtype} on {block.device}")
+
+
+def random_erase(x, block, out=None):
+    """Random erasing of (B, C, H, W) fp32 / bf16 images with the boxes and the noise key the device ``block`` holds at the
+    time the kernel runs: ``out`` = ``x`` outside the boxes, 0 or standard-normal noise inside.  Out of place by default;
+    ``out=x`` erases in place (only the boxes are touched)."""
+    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"random_erase: expected (B, C, H, W) fp32 or bf16 images, got {tuple(x.shape)} {x.dtype}")
+    _erase_block(x, block)
+    B, C, H, W = x.shape
+    if out is x:
+        if not x.is_contiguous():
+            raise RuntimeError("random_erase: in place needs a contiguous batch")
+    else:
+        x = x.contiguous()
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+            raise RuntimeError("random_erase: `out` must be a contiguous tensor of the input's shape, dtype and device")
+    rc = L.lib().fv_random_erase(L.ptr(x), L.ptr(out), L.i32(L.dtype_code(x.dtype)), L.i32(B), L.i32(C), L.i32(H), L.i32(W),
+                                 L.ptr(block), L.stream_of(x))
+    L.check(rc, "random_erase")
+    return out
+
+
+def patch_unfold_u8_re(x, table, ph, pw, out_dtype, erase):
+    """``patch_unfold(random_erase(table[c][x], erase), ph, pw, out_dtype)`` in the one launch of ``patch_unfold_u8``: the
+    pixels inside a sample's box are replaced between the lookup and the placement.  Applicable where
+    ``patch_unfold_u8_ok``."""
+    B, C, H, W = x.shape
+    _u8_table(x, table, C)
+    _erase_block(x, erase)
+    out = torch.empty(B, (H // ph) * (W // pw), C * ph * pw, device=x.device, dtype=out_dtype)
+    rc = L.lib().fv_patch_unfold_u8_re(L.ptr(x), L.ptr(table), L.ptr(out), L.i32(L.dtype_code(out_dtype)), L.i32(B), L.i32(C),
+                                       L.i32(H), L.i32(W), L.i32(ph), L.i32(pw), L.ptr(erase), L.stream_of(x))
+    L.check(rc, "patch_unfold_u8_re")
+    return out
+
+
+def patch_unfold_mix_u8_re(x, table, ph, pw, out_dtype, block, erase):
+    """``patch_unfold_mix(random_erase(table[c][x], erase), ph, pw, out_dtype, block)``: each image of a pair is erased
+    with its own box, then the two are mixed.  Applicable where ``patch_unfold_u8_ok`` and the batch is even."""
+    B, C, H, W = x.shape
+    _u8_table(x, table, C)
+    _erase_block(x, erase)
+    out = torch.empty(B, (H // ph) * (W // pw), C * ph * pw, device=x.device, dtype=out_dtype)
+    rc = L.lib().fv_patch_unfold_mix_u8_re(L.ptr(x), L.ptr(table), L.ptr(out), L.i32(L.dtype_code(out_dtype)), L.i32(B), L.i32(C),
+                                           L.i32(H), L.i32(W), L.i32(ph), L.i32(pw), L.ptr(block), L.ptr(erase), L.stream_of(x))
+    L.check(rc, "patch_unfold_mix_u8_re")
+    return out
+
+
 def gemm_rowbias(a, w, table):
     """fp32 (M, N) = bf16_round(a (M, K) @ w (N, K)^T) + table[m mod period]: bf16 operands, table (period, N) fp32."""
     M, K = a.shape

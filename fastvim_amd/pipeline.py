@@ -36,6 +36,13 @@ class SegmentedTrainStep:
     the batch is mixed inside the step with the parameters of the last ``mixup.sample()``, which the caller issues between
     steps like ``opt.set_lr``:  ``x.copy_(batch); labels.copy_(y); mixup.sample(); opt.set_lr(lr); step.step()``.
 
+    ``erase`` (a ``fastvim_amd.erasing.RandomErasing``): random erasing inside the step, after the normalisation and before the
+    mixing, with the boxes and the noise key of the last ``erase.sample()`` -- the caller's, between steps, like
+    ``mixup.sample()``; the step never draws.  A uint8 ``x`` is erased inside the patch unfold where that kernel applies;
+    otherwise, and for a float ``x``, one ``fv_random_erase`` launch writes the erased batch into a scratch buffer of the step
+    (never into ``x``: a replay without a fresh copy erases the same pixels again, nothing accumulates).  Not with ``hcs``:
+    the cell recipes do not erase.
+
     ``hcs`` (a ``fastvim_amd.hcs.ChannelSampler``, for the channel models: ``model._embed`` must take ``hcs=``): hierarchical
     channel sampling inside the step.  The caller draws between steps -- ``x.copy_(batch); target.copy_(y); hcs.sample();
     opt.set_lr(lr); step.step()`` -- and the step embeds the sampler's current subset: the indices are read from its device
@@ -49,7 +56,10 @@ class SegmentedTrainStep:
     step object leaves the model, the optimizer and the DropPath stream exactly as it found them."""
 
     def __init__(self, model, flat, opt, loss_fn, x, target, n_segments=3, amp_dtype=torch.bfloat16, use_graph=True,
-                 warmup=2, mixup=None, hcs=None):
+                 warmup=2, mixup=None, hcs=None, erase=None):
+        if erase is not None and hcs is not None:
+            raise ValueError("SegmentedTrainStep: erase= and hcs= do not combine (the channel recipes of the reference do not "
+                             "erase, and the per-channel unfold has no erase form)")
         self.model, self.flat, self.opt, self.loss_fn = model, flat, opt, loss_fn
         self.x, self.target, self.amp_dtype = x, target, amp_dtype
         # batch-mode Mixup / CutMix inside the step: the images are mixed on their way into the patch embedding by whatever
@@ -65,6 +75,17 @@ class SegmentedTrainStep:
                 # fp32: the mixed batch is a float buffer, what the embed would have been handed by a host-side loader)
                 self._x_mixed = torch.empty_like(x, memory_format=torch.contiguous_format,
                                                  dtype=torch.float32 if x.dtype == torch.uint8 else x.dtype)
+        # random erasing inside the step: the boxes and the key of erase's device block when the graph RUNS.  Inside the
+        # embedding (the uint8 unfold kernel) for a uint8 `x` and a model whose _embed takes `erase=`; else into `_x_erased`,
+        # after the table lookup and in front of the mixing
+        self.erase, self._embed_takes_erase, self._x_erased = erase, False, None
+        if erase is not None:
+            erase.bind(x)                                # batch and image size; the block exists before any capture
+            self._embed_takes_erase = (x.dtype == torch.uint8 and "erase" in inspect.signature(model._embed).parameters
+                                       and (mixup is None or self._embed_takes_mix))
+            if not self._embed_takes_erase:
+                self._x_erased = torch.empty_like(x, memory_format=torch.contiguous_format,
+                                                  dtype=torch.float32 if x.dtype == torch.uint8 else x.dtype)
         # hierarchical channel sampling: the subset of the sampler's device array, one family of graphs per channel count
         self.hcs = hcs
         if hcs is not None and "hcs" not in inspect.signature(model._embed).parameters:
@@ -99,12 +120,18 @@ class SegmentedTrainStep:
         cuts = []              # per run in FORWARD order: (inputs (leaves) or None, outputs)
         with torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.amp_dtype != torch.float32):
             kw = {} if self.hcs is None else {"hcs": self.hcs}
+            x = self.x
+            if self._embed_takes_erase:
+                kw["erase"] = self.erase
+            elif self.erase is not None:      # normalise, then erase out of place: `x` from here on is the float scratch batch
+                xin = pixels.normalise_like(m, x) if x.dtype == torch.uint8 else x
+                x = self.erase.erase(xin, out=self._x_erased)
             if self.mixup is None:
-                h, _ = m._embed(self.x, **kw)
+                h, _ = m._embed(x, **kw)
             elif self._embed_takes_mix:
-                h, _ = m._embed(self.x, mix=self.mixup, **kw)
+                h, _ = m._embed(x, mix=self.mixup, **kw)
             else:              # (the channel models: the whole image is mixed before channels are selected, the reference's order)
-                xin = pixels.normalise_like(m, self.x) if self.x.dtype == torch.uint8 else self.x
+                xin = pixels.normalise_like(m, x) if x.dtype == torch.uint8 else x
                 h, _ = m._embed(self.mixup.mix_batch(xin, out=self._x_mixed), **kw)
             res, pend = None, None
             fwd_runs = self.runs[::-1]

@@ -17,8 +17,11 @@ the loader -- and from the looked-up fp32 value on do what the float kernels do.
     step = SegmentedTrainStep(model, flat, opt, mix.criterion(), x, labels, mixup=mix)
     x.copy_(batch_u8, non_blocking=True); ...; step.step()
 
-Out of scope: random erasing, RandAugment, channels-last batches (they take the eager lookup below and then the float
-path, same values) and the MAE models, whose loss patchifies the float image.
+Random erasing acts on the normalised image and therefore happens after the lookup, on the device:
+``fastvim_amd.erasing.RandomErasing`` and ``SegmentedTrainStep(..., erase=re)``.
+
+Out of scope: RandAugment (a PIL stage: it stays 8-bit on the host), channels-last batches (they take the eager lookup below
+and then the float path, same values) and the MAE models, whose loss patchifies the float image.
 """
 import torch
 import torch.nn.functional as F

@@ -68,7 +68,9 @@ const char* fv_last_error(void);
  *      Later, still 3: fv_swap_params_ema and fv_eval_accumulate were ADDED (the validation step: the batch under the
  *      live and the EMA weights, metrics accumulated on the device).
  *      Later, still 3: fv_patch_unfold_u8, fv_patch_unfold_mix_u8 and fv_patch_unfold_chan_u8 were ADDED (8-bit image
- *      batches: the per-channel normalisation as a table lookup inside the patch unfold). */
+ *      batches: the per-channel normalisation as a table lookup inside the patch unfold).
+ *      Later, still 3: fv_random_erase, fv_patch_unfold_u8_re and fv_patch_unfold_mix_u8_re were ADDED (random erasing
+ *      of the normalised image, with the boxes and the noise key in device memory); no existing entry point changed. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -694,6 +696,28 @@ typedef struct fv_mix_params {
   int32_t reserved;
 } fv_mix_params;
 
+/* ------------------------------------------------------------------------
+ * Random erasing (timm.data.random_erasing.RandomErasing with count 1, as every ImageNet and MAE fine-tune loader of
+ * the reference applies it: after Normalize, before the batch-level Mixup).  Sample b has at most one box; inside it
+ * every pixel of every channel is replaced.  Like the mix parameters, boxes and noise key live in an ERASE BLOCK in
+ * device memory that the kernels read when they RUN -- 4 + 4 * batch int32, 16-byte aligned:
+ *   [0] key0, [1] key1   the Philox key of this draw (the host derives it from its (seed, counter))
+ *   [2] mode             FV_ERASE_CONST: write 0;  FV_ERASE_PIXEL: write a standard-normal value per (channel, y, x)
+ *   [3] batch            number of box records that follow; a sample at or past it is not erased
+ *   [4 + 4 b ..]         top, left, h, w of sample b, in pixels; h <= 0 (or w <= 0) means no erase
+ * The noise at (b, c, y, x) is a function of (key0, key1, b, c, y, x) alone (csrc/erase_noise.h): Philox4x32-10 with
+ * key (key0, key1) and counter (x >> 2, y, c, b); output words 0, 1 become pixels x & ~3 and (x & ~3) + 1 by Box-Muller
+ * (cos, sin), words 2, 3 the next two; u1 = ((r >> 8) + 1) * 2^-24, u2 = (r' >> 8) * 2^-24.  Every kernel below writes
+ * the same bits for the same key, whatever its load width, output type or workgroup shape.
+ * ---------------------------------------------------------------------- */
+#define FV_ERASE_CONST 0
+#define FV_ERASE_PIXEL 1
+/* out = x outside the boxes, 0 / noise inside; x, out (batch, chans, height, width) contiguous, of one dtype (fp32 or
+ * bf16: the fp32 noise rounded once).  out == x is allowed (then only the boxes are touched); any other overlap is
+ * not.  16-byte accesses where width and addresses allow, else 8, 4 or one element. */
+int fv_random_erase(const void* x, void* out, int dtype, int batch, int chans, int height, int width, const void* erase,
+                    fv_stream_t stream);
+
 /* out[b] = mix(x[b], x[batch-1-b]), out of place; x, out (batch, chans, height, width) of one dtype (fp32 or bf16),
  * batch even.  One thread handles the same position of both images of a pair: the batch is read once and written
  * once. */
@@ -774,6 +798,16 @@ int fv_patch_unfold_mix_u8(const uint8_t* img, const float* table, void* out, in
 int fv_patch_unfold_chan_u8(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans_total,
                             int height, int width, int ph, int pw, const int32_t* sel, int n_sel, int colwise,
                             fv_stream_t stream);
+/* The two launches above with random erasing between the lookup and the placement / the mixing: `erase` is the erase
+ * block described at fv_random_erase; in the pair launch each image of a pair is erased with its own box first and
+ * mixed afterwards (loader, then training_step).  Bit for bit
+ *   fv_patch_unfold_u8_re(img, table, erase)          == fv_patch_unfold(fv_random_erase(table[c][img]))
+ *   fv_patch_unfold_mix_u8_re(img, table, mix, erase) == fv_patch_unfold_mix(fv_random_erase(table[c][img]), mix) */
+int fv_patch_unfold_u8_re(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans,
+                          int height, int width, int ph, int pw, const void* erase, fv_stream_t stream);
+int fv_patch_unfold_mix_u8_re(const uint8_t* img, const float* table, void* out, int out_dtype, int batch, int chans,
+                              int height, int width, int ph, int pw, const void* mix, const void* erase,
+                              fv_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Fused AdamW (decoupled weight decay, bias correction; torch.optim.AdamW semantics) over a flat fp32
