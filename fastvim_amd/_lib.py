@@ -39,6 +39,7 @@ C_ABI_SYMBOLS = (
     "fv_swap_params_ema", "fv_eval_accumulate",
     "fv_patch_unfold_u8", "fv_patch_unfold_mix_u8", "fv_patch_unfold_chan_u8",
     "fv_random_erase", "fv_patch_unfold_u8_re", "fv_patch_unfold_mix_u8_re",
+    "fv_mae_loss_ok", "fv_mae_loss_fwd", "fv_mae_loss_bwd",
 )
 
 

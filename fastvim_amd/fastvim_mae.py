@@ -34,9 +34,10 @@ class MaskedAutoencoderViM(_FastVimMAE):
                  decoder_depth=8, norm_pix_loss=True, channels=3, ssm_cfg=None, drop_rate=0.0,
                  norm_epsilon: float = 1e-5, rms_norm: bool = False, initializer_cfg=None, fused_add_norm=False,
                  residual_in_fp32=False, device=None, dtype=None, init_layer_scale=None, use_norm_after_ssm=True,
-                 embed_layer=PatchEmbed, **kwargs):
+                 embed_layer=PatchEmbed, fused_loss=False, **kwargs):
         factory_kwargs = {"device": device, "dtype": dtype}
         nn.Module.__init__(self)          # (the FastVim MAE's constructor builds pooled mixers: not wanted here)
+        self.fused_loss = bool(fused_loss)
         self.residual_in_fp32 = residual_in_fp32
         self.fused_add_norm = fused_add_norm
         self.d_model = self.num_features = self.embed_dim = embed_dim

@@ -132,3 +132,86 @@ def top1_correct(logits, labels):
     """(B,) bool: ``logits.argmax(1) == labels`` (the first maximum on a tie), from the loss kernel's arg-max pass."""
     _, _, (rows, _) = _label_ce(logits, labels, None, 0.0, False, True)
     return rows.bool()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# MAE reconstruction loss (csrc/mae_loss.hip, C ABI ``fv_mae_loss_fwd`` / ``fv_mae_loss_bwd``)
+MAE_LOSS_MAX_PATCH = 28
+MAE_LOSS_MAX_PATCHES = 128 * 1024
+
+
+def mae_reconstruction_loss_ok(imgs, pred, mask, patch_size, table=None):
+    """Whether ``mae_reconstruction_loss`` takes these tensors: the shape rule of the C predicate ``fv_mae_loss_ok`` (3
+    channels, square images of whole patches, patch even in [8, 28], ``pred`` fp32 or bf16, at most 128 x 1024 patches) plus
+    what only the host sees: GPU tensors on one device, NCHW-contiguous images (fp32, or uint8 with a (3, 256) fp32 table)
+    that do not require grad, a contiguous ``pred`` (N, L, 3 p^2) and a contiguous fp32 ``mask`` (N, L).  Pure Python: no
+    GPU and no library needed to ask."""
+    p = int(patch_size)
+    if imgs.dim() != 4 or pred.dim() != 3 or mask.dim() != 2:
+        return False
+    N, C, H, W = imgs.shape
+    if N <= 0 or C != 3 or H <= 0 or H != W or p < 8 or p > MAE_LOSS_MAX_PATCH or p % 2 or H % p:
+        return False
+    Lp = (H // p) * (W // p)
+    if N * Lp > MAE_LOSS_MAX_PATCHES or pred.dtype not in (torch.float32, torch.bfloat16):
+        return False
+    if tuple(pred.shape) != (N, Lp, 3 * p * p) or tuple(mask.shape) != (N, Lp) or mask.dtype != torch.float32:
+        return False
+    if not (imgs.is_cuda and pred.device == imgs.device and mask.device == imgs.device):
+        return False
+    if not (imgs.is_contiguous() and pred.is_contiguous() and mask.is_contiguous()):
+        return False
+    if imgs.requires_grad or mask.requires_grad:
+        return False
+    if table is None:
+        return imgs.dtype == torch.float32
+    return (imgs.dtype == torch.uint8 and table.dtype == torch.float32 and tuple(table.shape) == (3, 256)
+            and table.is_contiguous() and table.device == imgs.device and table.data_ptr() % 16 == 0)
+
+
+class _MAELossFn(torch.autograd.Function):
+    """Differentiable in ``pred`` only.  Saves (mean, rstd) per patch and sum(mask) -- both stay on the device, nothing is
+    synchronised: safe under graph capture -- and recomputes the target from the image in the backward launch."""
+
+    @staticmethod
+    def forward(ctx, pred, imgs, mask, table, patch, norm_pix):
+        N, Lp, D = pred.shape
+        dev = pred.device
+        rows = torch.empty(N, Lp, device=dev, dtype=torch.float32)
+        stats = torch.empty(N, Lp, 2, device=dev, dtype=torch.float32)
+        out = torch.empty(2, device=dev, dtype=torch.float32)
+        rc = L.lib().fv_mae_loss_fwd(L.ptr(imgs), L.ptr(table), L.ptr(pred), L.i32(L.dtype_code(pred.dtype)), L.ptr(mask),
+                                     L.ptr(rows), L.ptr(stats), L.ptr(out), L.i32(N), L.i32(imgs.shape[2]), L.i32(imgs.shape[3]),
+                                     L.i32(patch), L.i32(1 if norm_pix else 0), L.stream_of(pred))
+        L.check(rc, "mae_loss_fwd")
+        ctx.save_for_backward(pred, imgs, mask, table, stats, out)
+        ctx.patch = patch
+        ctx.mark_non_differentiable(rows, stats)
+        return out[0], rows, stats
+
+    @staticmethod
+    def backward(ctx, g, _g_rows, _g_stats):
+        pred, imgs, mask, table, stats, out = ctx.saved_tensors
+        g = g.detach().to(device=pred.device, dtype=torch.float32).reshape(1).contiguous()
+        dpred = torch.empty_like(pred)
+        rc = L.lib().fv_mae_loss_bwd(L.ptr(imgs), L.ptr(table), L.ptr(pred), L.i32(L.dtype_code(pred.dtype)), L.ptr(mask),
+                                     L.ptr(stats), L.ptr(out[1:]), L.ptr(g), L.ptr(dpred), L.i32(pred.shape[0]),
+                                     L.i32(imgs.shape[2]), L.i32(imgs.shape[3]), L.i32(ctx.patch), L.stream_of(pred))
+        L.check(rc, "mae_loss_bwd")
+        return dpred, None, None, None, None, None
+
+
+def mae_reconstruction_loss(imgs, pred, mask, patch_size, norm_pix_loss=True, table=None, return_rows=False):
+    """The MAE loss of ``MaskedAutoencoderViM.forward_loss`` from two launches (and one backward): ``imgs`` (N, 3, H, W) fp32,
+    or uint8 with ``table`` (the (3, 256) fp32 table of ``fastvim_amd.pixels``), ``pred`` (N, L, 3 p^2) fp32 or bf16 (inside
+    ``torch.autocast`` it simply arrives as bf16; the arithmetic is fp32), ``mask`` (N, L) fp32 with 1 = removed.  Returns
+    the scalar fp32 loss, differentiable in ``pred`` (the gradient has ``pred``'s dtype); with ``return_rows`` also
+    ``loss_rows`` (N, L), the per-patch mean squared error (0 on kept patches), for logging.  The uint8 form equals the float
+    form on ``pixels.lookup(table, imgs)`` bit for bit.  Raises where ``mae_reconstruction_loss_ok`` says no: the caller
+    chooses the fallback."""
+    if not mae_reconstruction_loss_ok(imgs, pred, mask, patch_size, table):
+        raise RuntimeError(f"mae_reconstruction_loss: unsupported arguments (images {tuple(imgs.shape)} {imgs.dtype}, pred "
+                           f"{tuple(pred.shape)} {pred.dtype}, mask {tuple(mask.shape)} {mask.dtype}, patch {patch_size}, "
+                           f"table {'given' if table is not None else 'none'}); see mae_reconstruction_loss_ok")
+    loss, rows, _ = _MAELossFn.apply(pred, imgs, mask, table, int(patch_size), bool(norm_pix_loss))
+    return (loss, rows) if return_rows else loss

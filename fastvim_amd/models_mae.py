@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
+from . import losses, pixels
 from .fastvim import PatchEmbed, _compute_dtype, _init_weights, trunc_normal_
 from .layernorm import RMSNorm, layer_norm_fn
 from .mamba_simple_faster import linear_module
@@ -129,14 +130,19 @@ def create_block_masked(d_model, ssm_cfg=None, norm_epsilon=1e-5, rms_norm=False
 
 
 class MaskedAutoencoderViM(nn.Module):
+    # Float images: True sends the loss through the fused kernel (fastvim_amd/losses.py), False keeps the eager
+    # composition of ``forward_loss``.  uint8 images take the kernel either way.  A plain attribute: it may be set later.
+    fused_loss = False
+
     def __init__(self, img_size=224, patch_size=16, stride=16, depth=24, embed_dim=192, decoder_embed_dim=512,
                  decoder_depth=2, norm_pix_loss=True, channels=3, ssm_cfg=None, drop_rate=0.0,
                  norm_epsilon: float = 1e-5, rms_norm: bool = False, initializer_cfg=None, fused_add_norm=False,
                  residual_in_fp32=False, device=None, dtype=None, init_layer_scale=None, use_norm_after_ssm=True,
                  embed_layer=PatchEmbed, scanpath_type="rowwise", rotate_every_block=True, collapse_method="mean",
-                 **kwargs):
+                 fused_loss=False, **kwargs):
         factory_kwargs = {"device": device, "dtype": dtype}
         super().__init__()
+        self.fused_loss = bool(fused_loss)
         self.residual_in_fp32 = residual_in_fp32
         self.fused_add_norm = fused_add_norm
         self.rotate_every_block = rotate_every_block
@@ -275,15 +281,31 @@ class MaskedAutoencoderViM(nn.Module):
         loss = ((pred - target) ** 2).mean(dim=-1)
         return (loss * mask).sum() / mask.sum()
 
+    def reconstruction_loss(self, imgs, pred, mask, table=None):
+        """The loss ``forward`` computes.  uint8 ``imgs`` (with ``table``, the patch embedding's pixel table) take the fused
+        kernel (fastvim_amd/losses.py: ``mae_reconstruction_loss``, which looks the pixels up itself); float images take it
+        when ``self.fused_loss`` is set.  Where its predicate says no -- a ragged size under ``dynamic_img_pad``, channels
+        other than 3, a CPU batch, a non-contiguous ``pred``, images that require grad -- uint8 images are looked up eagerly
+        and the float composition ``forward_loss`` runs (same values up to rounding)."""
+        if table is not None or self.fused_loss:
+            p = self.patch_embed.patch_size[0]
+            m = mask if mask.dtype == torch.float32 else mask.float()
+            if losses.mae_reconstruction_loss_ok(imgs, pred, m, p, table):
+                return losses.mae_reconstruction_loss(imgs, pred, m, p, self.norm_pix_loss, table)
+        if table is not None:
+            imgs = pixels.lookup(table, imgs)
+        return self.forward_loss(imgs, pred, mask)
+
     def forward(self, imgs, mask_ratio=0.75, inference_params=None, noise=None):
-        """``imgs``: normalised float images.  uint8 batches (fastvim_amd/pixels.py) are out of scope here: the loss
-        patchifies the float image."""
-        if imgs.dtype == torch.uint8:
-            raise TypeError("MaskedAutoencoderViM: uint8 images are not supported (the reconstruction loss patchifies the "
-                            "normalised float image); normalise the batch first, e.g. with fastvim_amd.pixels.PixelNorm")
+        """``imgs``: normalised float images, or a uint8 batch once ``fastvim_amd.pixels.attach_pixel_norm`` has put the
+        normalisation table on the model: the patch embedding and the loss then look the pixels up inside their kernels."""
+        table = pixels.pixel_table(self.patch_embed, imgs) if imgs.dtype == torch.uint8 else None
         latent, mask, ids_restore = self.forward_encoder(imgs, mask_ratio, inference_params, noise=noise)
         pred = self.forward_decoder(latent, ids_restore, inference_params)
-        loss = self.forward_loss(imgs, pred, mask)
+        if table is None and not self.fused_loss:
+            loss = self.forward_loss(imgs, pred, mask)
+        else:
+            loss = self.reconstruction_loss(imgs, pred, mask, table)
         return loss, pred, mask
 
 

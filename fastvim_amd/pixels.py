@@ -20,8 +20,11 @@ the loader -- and from the looked-up fp32 value on do what the float kernels do.
 Random erasing acts on the normalised image and therefore happens after the lookup, on the device:
 ``fastvim_amd.erasing.RandomErasing`` and ``SegmentedTrainStep(..., erase=re)``.
 
-Out of scope: RandAugment (a PIL stage: it stays 8-bit on the host), channels-last batches (they take the eager lookup below
-and then the float path, same values) and the MAE models, whose loss patchifies the float image.
+The MAE models (``fastvim_amd.models_mae``, ``fastvim_amd.fastvim_mae``) take uint8 batches as well: their reconstruction
+loss looks the pixels up inside its own kernel (``fastvim_amd.losses.mae_reconstruction_loss``, csrc/mae_loss.hip).
+
+Out of scope: RandAugment (a PIL stage: it stays 8-bit on the host) and channels-last batches (they take the eager lookup below
+and then the float path, same values).
 """
 import torch
 import torch.nn.functional as F

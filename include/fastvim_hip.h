@@ -70,7 +70,9 @@ const char* fv_last_error(void);
  *      Later, still 3: fv_patch_unfold_u8, fv_patch_unfold_mix_u8 and fv_patch_unfold_chan_u8 were ADDED (8-bit image
  *      batches: the per-channel normalisation as a table lookup inside the patch unfold).
  *      Later, still 3: fv_random_erase, fv_patch_unfold_u8_re and fv_patch_unfold_mix_u8_re were ADDED (random erasing
- *      of the normalised image, with the boxes and the noise key in device memory); no existing entry point changed. */
+ *      of the normalised image, with the boxes and the noise key in device memory); no existing entry point changed.
+ *      Later, still 3: fv_mae_loss_ok, fv_mae_loss_fwd and fv_mae_loss_bwd were ADDED (the MAE reconstruction loss, from
+ *      fp32 or uint8 images, fused into two launches forward and one backward); no existing entry point changed. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -941,6 +943,44 @@ int fv_lars_flat(float* params, const float* grads, float* momentum_buf, void* s
 int fv_swap_params_ema(float* params, float* ema, void* shadow, int shadow_dtype, size_t n, fv_stream_t stream);
 int fv_eval_accumulate(const void* logits, int logits_dtype, const int64_t* labels, const int32_t* n_valid,
                        float* loss_rows, int32_t* correct_rows, int64_t* acc, int batch, int classes, fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * The MAE reconstruction loss (models/mae/models_mamba_faster_mae_vimdecoder.py:864-880, forward_loss): mean squared error
+ * between the prediction and the (per-patch normalised) pixels, averaged over the removed patches.
+ *
+ *   img        (batch, 3, height, width), contiguous.  table == NULL: fp32 (the normalised images).  table != NULL: uint8,
+ *              and a pixel is table[c][v]; table is the (3, 256) fp32 table of fv_patch_unfold_u8, 16-byte aligned
+ *   pred       (batch, L, D) fp32 or bf16 (pred_dtype), contiguous; L = (height / patch) (width / patch), D = 3 patch^2;
+ *              patch l = gy (width / patch) + gx, element j = (py patch + px) 3 + c is pixel (c, gy patch + py, gx patch + px)
+ *   mask       (batch, L) fp32: 0 = kept, else the patch's weight (1 = removed)
+ *   loss_rows  (batch, L) fp32 out: sum_j (pred[j] - target[j])^2 / D; exactly 0 where mask == 0
+ *   row_stats  (batch, L, 2) fp32 out: (mean, rstd) of the patch, (0, 1) without norm_pix, (0, 0) where mask == 0
+ *   out        2 floats out: out[0] = sum(loss_rows mask) / sum(mask), out[1] = sum(mask)
+ * norm_pix != 0: mean = sum(t) / D, var = sum((t - mean)^2) / (D - 1) -- exact fp32 passes over the on-chip copy of the
+ *   patch, the mean first (refined once by the sum of the residuals), never E[t^2] - mean^2: a constant patch has var 0
+ *   and target 0 exactly --, target = (t - mean) rsqrt(var + 1e-6); norm_pix == 0: target = t.
+ * A patch with mask == 0 is not read: neither its pixels nor its pred row, whatever they hold.
+ *
+ * fv_mae_loss_fwd: two launches (the rows, then one workgroup that sums loss_rows mask and mask in fp64 in a fixed order);
+ *   no atomics: the same inputs give the same bits.
+ * fv_mae_loss_bwd: one launch.  dpred[n, l, j] = g mask[n, l] 2 (pred - target) / (D sum_mask) in pred_dtype, with target
+ *   recomputed from img and the row_stats of the forward call; exactly 0, with nothing read, where mask == 0.  g and
+ *   sum_mask are single fp32 values in DEVICE memory (sum_mask: out + 1 of the forward call).
+ * fv_mae_loss_ok: host code; 1 when both accept the shape: chans == 3, height == width, a multiple of patch, patch even
+ *   in [8, 28], pred fp32 or bf16, batch L <= 131072.
+ * Alignment: every buffer that of its element type only (uint8 images: none), the table 16 bytes; the kernels pick their
+ *   access widths from the actual addresses.
+ * Bit identity: a call with a table equals the call with table == NULL on the fp32 image table[c][img] in every output --
+ *   loss_rows, row_stats, out, dpred.  The uint8 form only looks values up (no arithmetic on the byte).
+ * sum(mask) == 0 is unspecified (0 / 0, as in the reference).
+ * ---------------------------------------------------------------------- */
+int fv_mae_loss_ok(int batch, int chans, int height, int width, int patch, int pred_dtype);
+int fv_mae_loss_fwd(const void* img, const float* table, const void* pred, int pred_dtype, const float* mask,
+                    float* loss_rows, float* row_stats, float* out, int batch, int height, int width, int patch,
+                    int norm_pix, fv_stream_t stream);
+int fv_mae_loss_bwd(const void* img, const float* table, const void* pred, int pred_dtype, const float* mask,
+                    const float* row_stats, const float* sum_mask, const float* g, void* dpred, int batch, int height,
+                    int width, int patch, fv_stream_t stream);
 
 #ifdef __cplusplus
 }
