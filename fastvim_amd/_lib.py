@@ -40,6 +40,7 @@ C_ABI_SYMBOLS = (
     "fv_patch_unfold_u8", "fv_patch_unfold_mix_u8", "fv_patch_unfold_chan_u8",
     "fv_random_erase", "fv_patch_unfold_u8_re", "fv_patch_unfold_mix_u8_re",
     "fv_mae_loss_ok", "fv_mae_loss_fwd", "fv_mae_loss_bwd",
+    "fv_mae_mask_plan", "fv_tokens_gather", "fv_mae_decoder_tokens_fwd", "fv_mae_decoder_tokens_bwd",
 )
 
 

@@ -34,10 +34,11 @@ class MaskedAutoencoderViM(_FastVimMAE):
                  decoder_depth=8, norm_pix_loss=True, channels=3, ssm_cfg=None, drop_rate=0.0,
                  norm_epsilon: float = 1e-5, rms_norm: bool = False, initializer_cfg=None, fused_add_norm=False,
                  residual_in_fp32=False, device=None, dtype=None, init_layer_scale=None, use_norm_after_ssm=True,
-                 embed_layer=PatchEmbed, fused_loss=False, **kwargs):
+                 embed_layer=PatchEmbed, fused_loss=False, fused_tokens=False, **kwargs):
         factory_kwargs = {"device": device, "dtype": dtype}
         nn.Module.__init__(self)          # (the FastVim MAE's constructor builds pooled mixers: not wanted here)
         self.fused_loss = bool(fused_loss)
+        self.fused_tokens = bool(fused_tokens)
         self.residual_in_fp32 = residual_in_fp32
         self.fused_add_norm = fused_add_norm
         self.d_model = self.num_features = self.embed_dim = embed_dim
@@ -99,6 +100,11 @@ class MaskedAutoencoderViM(_FastVimMAE):
         for layer in self.layers:
             hidden_states, residual = layer(hidden_states, residual, inference_params=inference_params)
         return self._final_norm(self.norm_f, hidden_states, residual), mask, ids_restore
+
+    def _encode(self, x, mask_ratio, inference_params=None, noise=None):
+        # ``fused_tokens`` reaches the inherited ``random_masking`` only: the decoder assembly below, with its class token,
+        # keeps the torch chain, so no plan is handed on
+        return (*self.forward_encoder(x, mask_ratio, inference_params, noise=noise), None)
 
     def forward_decoder(self, x, ids_restore, inference_params=None):
         """:633-691: mask tokens appended and unshuffled WITHOUT the class token, which is re-attached at the END of the

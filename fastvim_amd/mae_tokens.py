@@ -1,0 +1,185 @@
+"""Token bookkeeping of the MAE masked encoder on the HIP path (csrc/mae_tokens.hip; ``MaskedAutoencoderViM.fused_tokens``).
+
+Everything ``random_masking``, the odd ``Block_masked`` layers and the masked mixers derive from the (N, L) masking noise --
+which tokens are kept, the unshuffle index, the mask, the kept tokens' order in the transposed grid and its inverse, the
+mixers' (2, B, K) row indices of both layer parities -- comes from ONE launch per step (``mask_plan`` -> ``TokenPlan``).  The
+row copies that use it (``gather_tokens``: the masking gather, the odd layers' permute and un-permute) and the decoder's input
+assembly (``decoder_tokens``) are ``autograd.Function``s over plain gather kernels: the indices are unique, so the adjoint of
+a gather is the gather by the inverse index -- one pass, no zero fill, no atomics, and bit-identical to the
+``torch.gather`` composition and its autograd.  The one value that is not bit-identical is the gradient of ``mask_token``: a
+sum over the removed rows, here in fp64 in a fixed order (deterministic), in eager in whatever order the reduction takes.
+
+Nothing here synchronises with the host; outputs are allocated by torch on the current stream: safe under graph capture.
+"""
+from typing import NamedTuple
+
+import torch
+
+from . import _lib as L
+
+MAX_TOKENS = 1024                # FV_MAE_PLAN_MAX_TOKENS: 32 x 32, FastVim-H at 448 px
+MIN_KEEP = 3                     # the masked mixer's conv halo
+DECODER_ROWS_PER_BLOCK = 32      # FV_MAE_DECODER_ROWS_PER_BLOCK
+_DTYPES = (torch.float32, torch.bfloat16)
+
+
+class TokenPlan(NamedTuple):
+    """What one ``fv_mae_mask_plan`` launch writes; B samples, L = H W tokens, K kept.  The int64 tensors are what the eager
+    model computes (and returns); the int32 ones feed the kernels."""
+    ids_keep: torch.Tensor          # (B, K) int64, ascending positions of the kept tokens
+    ids_restore: torch.Tensor       # (B, L) int64: a kept token's place among the kept ones, a removed token's rank
+    mask: torch.Tensor              # (B, L) fp32, 1 = removed
+    keep_index: torch.Tensor        # (B, K) int32 = ids_keep
+    restore_index: torch.Tensor     # (B, L) int32 = ids_restore where < K, else -1
+    row_index_even: torch.Tensor    # (2, B, K) int32: the even mixers' [r, (H - 1) - flip(r)], r = ids_keep // W
+    ids_keep_odd: torch.Tensor      # (B, K) int64: the kept tokens' places in the transposed grid, ascending
+    order: torch.Tensor             # (B, K) int64: kept tokens in the transposed grid's scan order
+    inverse: torch.Tensor           # (B, K) int64: argsort(order)
+    order_index: torch.Tensor       # (B, K) int32 = order
+    inverse_index: torch.Tensor     # (B, K) int32 = inverse
+    row_index_odd: torch.Tensor     # (2, B, K) int32: the odd mixers' [r, (W - 1) - flip(r)], r = ids_keep_odd // H
+    token_size: tuple               # (H, W)
+
+
+def mask_plan_ok(noise, token_size, len_keep):
+    """Whether ``mask_plan`` takes these arguments: (N, L) fp32 contiguous noise on the GPU, L = H W <= 1024,
+    3 <= len_keep <= L.  Pure Python: no GPU and no library needed to ask."""
+    H, W = int(token_size[0]), int(token_size[1])
+    if not isinstance(noise, torch.Tensor) or noise.dim() != 2 or not noise.is_cuda:
+        return False
+    if noise.dtype != torch.float32 or not noise.is_contiguous() or noise.data_ptr() % 4 != 0:
+        return False
+    N, Ln = noise.shape
+    if N <= 0 or H <= 0 or W <= 0 or Ln != H * W or Ln > MAX_TOKENS:
+        return False
+    return MIN_KEEP <= int(len_keep) <= Ln
+
+
+def mask_plan(noise, token_size, len_keep):
+    """The masking plan of ``noise`` (N, L): one launch.  The K = ``len_keep`` tokens of lowest noise are kept, ties broken
+    by position (``torch.argsort(stable=True)``).  Finite noise is the contract; NaN noise gives an unspecified plan whose
+    indices are still all in range.  Raises where ``mask_plan_ok`` says no: the caller chooses the fallback."""
+    if not mask_plan_ok(noise, token_size, len_keep):
+        raise RuntimeError(f"mask_plan: unsupported arguments (noise {tuple(noise.shape)} {noise.dtype} on {noise.device}, "
+                           f"token_size {tuple(token_size)}, len_keep {len_keep}); see mask_plan_ok")
+    H, W, K = int(token_size[0]), int(token_size[1]), int(len_keep)
+    noise = noise.detach()
+    N, Ln = noise.shape
+    dev = noise.device
+    i64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int64)
+    i32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int32)
+    plan = TokenPlan(ids_keep=i64(N, K), ids_restore=i64(N, Ln), mask=torch.empty(N, Ln, device=dev, dtype=torch.float32),
+                     keep_index=i32(N, K), restore_index=i32(N, Ln), row_index_even=i32(2, N, K), ids_keep_odd=i64(N, K),
+                     order=i64(N, K), inverse=i64(N, K), order_index=i32(N, K), inverse_index=i32(N, K),
+                     row_index_odd=i32(2, N, K), token_size=(H, W))
+    rc = L.lib().fv_mae_mask_plan(L.ptr(noise), L.ptr(plan.ids_keep), L.ptr(plan.ids_restore), L.ptr(plan.mask),
+                                  L.ptr(plan.keep_index), L.ptr(plan.restore_index), L.ptr(plan.row_index_even),
+                                  L.ptr(plan.ids_keep_odd), L.ptr(plan.order), L.ptr(plan.inverse), L.ptr(plan.order_index),
+                                  L.ptr(plan.inverse_index), L.ptr(plan.row_index_odd), L.i32(N), L.i32(H), L.i32(W), L.i32(K),
+                                  L.stream_of(noise))
+    L.check(rc, "mae_mask_plan")
+    return plan
+
+
+def _gather(x, index, out_dtype):
+    """x (B, Lin, D) fp32 / bf16 contiguous, index (B, Lout) int32 -> (B, Lout, D) ``out_dtype``; one launch."""
+    B, Lin, D = x.shape
+    Lout = index.shape[1]
+    out = torch.empty(B, Lout, D, device=x.device, dtype=out_dtype)
+    rc = L.lib().fv_tokens_gather(L.ptr(x), L.i32(L.dtype_code(x.dtype)), L.ptr(index), L.ptr(out), L.i32(L.dtype_code(out_dtype)),
+                                  L.i32(B), L.i32(Lin), L.i32(Lout), L.i32(D), L.stream_of(x))
+    L.check(rc, "tokens_gather")
+    return out
+
+
+def _check_rows(who, x, index):
+    L.require_gpu(x, index)
+    if x.dim() != 3 or x.dtype not in _DTYPES or x.shape[-1] % 4 != 0:
+        raise RuntimeError(f"{who}: rows must be (B, L, D) fp32 or bf16 with D % 4 == 0, got {tuple(x.shape)} {x.dtype}")
+    if index.dim() != 2 or index.dtype != torch.int32 or index.shape[0] != x.shape[0] or not index.is_contiguous():
+        raise RuntimeError(f"{who}: the index must be a contiguous (B, L_out) int32 tensor, got {tuple(index.shape)} {index.dtype}")
+
+
+class _GatherTokensFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, index, adjoint_index):
+        ctx.save_for_backward(adjoint_index)
+        ctx.x_dtype = x.dtype
+        return _gather(x.contiguous(), index, x.dtype)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (adjoint_index,) = ctx.saved_tensors
+        if dout.dtype not in _DTYPES:
+            dout = dout.float()
+        return _gather(dout.contiguous(), adjoint_index, ctx.x_dtype), None, None
+
+
+def gather_tokens(x, index, adjoint_index):
+    """``out[b, t, :] = x[b, index[b, t], :]`` (a zero row where the index is negative) in ``x``'s dtype, bit-exact.
+    ``index`` (B, L_out) int32 must not pick a row twice; ``adjoint_index`` (B, L_in) int32 is its inverse -- the ``t`` with
+    ``index[b, t] == l``, -1 where row ``l`` is not picked -- and makes the backward one more gather: a ``TokenPlan``'s
+    (``keep_index``, ``restore_index``) and (``order_index``, ``inverse_index``), either way round, are such pairs."""
+    _check_rows("gather_tokens", x, index)
+    _check_rows("gather_tokens", x, adjoint_index)
+    if adjoint_index.shape[1] != x.shape[1]:
+        raise RuntimeError(f"gather_tokens: adjoint_index {tuple(adjoint_index.shape)} must have one entry per row of x "
+                           f"{tuple(x.shape)}")
+    return _GatherTokensFn.apply(x, index, adjoint_index)
+
+
+def decoder_tokens_ok(x, mask_token, pos_embed, plan):
+    """Whether ``decoder_tokens`` takes these tensors (the model's fallback is the eager chain)."""
+    if x.dim() != 3 or not x.is_cuda or x.dtype not in _DTYPES or x.shape[-1] % 4 != 0:
+        return False
+    B, K, D = x.shape
+    Ln = plan.restore_index.shape[1]
+    if tuple(plan.restore_index.shape) != (B, Ln) or plan.keep_index.shape[1] != K or plan.restore_index.device != x.device:
+        return False
+    return (mask_token.dtype == torch.float32 and mask_token.numel() == D and mask_token.is_contiguous()
+            and pos_embed.dtype == torch.float32 and pos_embed.numel() == Ln * D and pos_embed.is_contiguous()
+            and mask_token.device == x.device and pos_embed.device == x.device and not pos_embed.requires_grad)
+
+
+class _DecoderTokensFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mask_token, pos_embed, restore_index):
+        B, K, D = x.shape
+        Ln = restore_index.shape[1]
+        xc = x.contiguous()
+        out = torch.empty(B, Ln, D, device=x.device, dtype=torch.float32)
+        rc = L.lib().fv_mae_decoder_tokens_fwd(L.ptr(xc), L.i32(L.dtype_code(xc.dtype)), L.ptr(mask_token), L.ptr(pos_embed),
+                                               L.ptr(restore_index), L.ptr(out), L.i32(B), L.i32(Ln), L.i32(K), L.i32(D),
+                                               L.stream_of(xc))
+        L.check(rc, "mae_decoder_tokens_fwd")
+        ctx.save_for_backward(restore_index)
+        ctx.geo = (B, Ln, K, D, x.dtype, tuple(mask_token.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (restore_index,) = ctx.saved_tensors
+        B, Ln, K, D, x_dtype, mt_shape = ctx.geo
+        dout = dout.float().contiguous()
+        dx = torch.empty(B, K, D, device=dout.device, dtype=x_dtype)
+        nblocks = -(-(B * Ln) // DECODER_ROWS_PER_BLOCK)
+        partials = torch.empty(nblocks, D, device=dout.device, dtype=torch.float64)
+        dmt = torch.empty(D, device=dout.device, dtype=torch.float32)
+        rc = L.lib().fv_mae_decoder_tokens_bwd(L.ptr(dout), L.ptr(restore_index), L.ptr(dx), L.i32(L.dtype_code(x_dtype)),
+                                               L.ptr(partials), L.i32(nblocks), L.ptr(dmt), L.i32(B), L.i32(Ln), L.i32(K),
+                                               L.i32(D), L.stream_of(dout))
+        L.check(rc, "mae_decoder_tokens_bwd")
+        return dx, dmt.view(mt_shape), None, None
+
+
+def decoder_tokens(x, mask_token, pos_embed, plan):
+    """The MAE decoder's input from one launch: ``x`` (B, K, D) fp32 or bf16, the kept tokens after ``decoder_embed``;
+    ``mask_token`` (1, 1, D) fp32; ``pos_embed`` (1, L, D) fp32, no gradient; ``plan`` a ``TokenPlan`` of the same step ->
+    (B, L, D) fp32 = (kept token, or ``mask_token`` rounded to ``x``'s dtype) + ``pos_embed``: the values, dtype and single
+    rounding of the eager ``repeat / cat / gather / add`` chain.  Backward: ``dx`` bit-identical to autograd's; ``d mask_token``
+    the sum of the removed rows (rounded to ``x``'s dtype first, as autograd rounds them) in fp64 in a fixed order."""
+    if not decoder_tokens_ok(x, mask_token, pos_embed, plan):
+        raise RuntimeError(f"decoder_tokens: unsupported arguments (x {tuple(x.shape)} {x.dtype}, mask_token "
+                           f"{tuple(mask_token.shape)} {mask_token.dtype}, pos_embed {tuple(pos_embed.shape)} {pos_embed.dtype}); "
+                           "see decoder_tokens_ok")
+    return _DecoderTokensFn.apply(x, mask_token, pos_embed, plan.restore_index)

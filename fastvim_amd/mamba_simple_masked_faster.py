@@ -32,19 +32,25 @@ class MaskedFastVimMixerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hidden, ids_keep, W_in, b_in, cw, cb, cw_b, cb_b, Wx, Wx_b, Wdt, bdt, Wdt_b, bdt_b, A_log, A_b_log,
-                D, D_b, ln_w, ln_b, W_out, b_out, rows, cols, ln_eps, cdt):
+                D, D_b, ln_w, ln_b, W_out, b_out, rows, cols, ln_eps, cdt, row_index=None):
         L.require_gpu(hidden)
         B, Lk, d = hidden.shape
         if ids_keep.shape != (B, Lk):
             raise RuntimeError(f"Mamba_masked: ids_keep {tuple(ids_keep.shape)} does not match hidden {tuple(hidden.shape)}")
         if Lk < 3:
             raise RuntimeError("Mamba_masked: needs at least 3 kept tokens (conv halo)")
+        if row_index is not None and (row_index.shape != (2, B, Lk) or row_index.dtype != torch.int32
+                                      or not row_index.is_contiguous() or row_index.device != hidden.device):
+            raise RuntimeError(f"Mamba_masked: row_index must be a contiguous (2, {B}, {Lk}) int32 tensor on {hidden.device}")
         d_in = W_in.shape[0] // 2
         srows = _split_rows(Lk)                 # un-pooled kernel geometry: srows x 1 x t, contiguous sequence
         t = Lk // srows
         with torch.autocast("cuda", enabled=False):
-            r = torch.div(ids_keep, cols, rounding_mode="floor").to(torch.int32)          # row of kept token t
-            idx = torch.stack([r, (rows - 1) - r.flip(1)]).contiguous()                   # (2, B, Lk)
+            if row_index is None:
+                r = torch.div(ids_keep, cols, rounding_mode="floor").to(torch.int32)      # row of kept token t
+                idx = torch.stack([r, (rows - 1) - r.flip(1)]).contiguous()               # (2, B, Lk)
+            else:
+                idx = row_index                                                           # the same array, from the step's plan
             h_c = hidden.to(cdt).contiguous()
             W_in_c, W_out_c = _shadow(W_in, cdt), _shadow(W_out, cdt)
             xz = linear_fwd(h_c.view(B * Lk, d), W_in_c, b_in).view(B, Lk, 2 * d_in)
@@ -107,7 +113,7 @@ class MaskedFastVimMixerFn(torch.autograd.Function):
         g_lw = p1[0] if ln_w is not None else None
         g_lb = p1[1] if ln_w is not None else None
         return (dhidden, None, dW_in, db_in, g_cw, g_cb, g_cwb, g_cbb, dWx2[0], dWx2[1], g_Wdt[0], g_bdt[0], g_Wdt[1],
-                g_bdt[1], g_A[0], g_A[1], g_D, g_Db, g_lw, g_lb, dW_out, db_out, None, None, None, None)
+                g_bdt[1], g_A[0], g_A[1], g_D, g_Db, g_lw, g_lb, dW_out, db_out, None, None, None, None, None)
 
 
 class Mamba_masked(_FastVimMamba):
@@ -127,8 +133,10 @@ class Mamba_masked(_FastVimMamba):
                          scaling_factor=1)
         del self.scaling_factor, self.use_our_selective_scan
 
-    def forward(self, hidden_states, ids_keep, inference_params=None):
+    def forward(self, hidden_states, ids_keep, inference_params=None, row_index=None):
         """hidden_states: (B, Lk, D) kept tokens; ids_keep: (B, Lk) integer positions in the rows x cols grid.
+        ``row_index``: the (2, B, Lk) int32 array ``[r, (rows - 1) - flip(r)]``, ``r = ids_keep // cols``, when the caller
+        already has it (fastvim_amd/mae_tokens.py computes it once per step); None: it is derived from ``ids_keep`` here.
         Returns (B, Lk, D)."""
         if inference_params is not None:
             raise NotImplementedError("FastVim mixers have no inference cache (reference: no step())")
@@ -145,7 +153,7 @@ class Mamba_masked(_FastVimMamba):
             self.dt_proj.weight, self.dt_proj.bias, self.dt_proj_b.weight, self.dt_proj_b.bias,
             self.A_log, self.A_b_log, self.D, self.D_b, ln_w, ln_b,
             self.out_proj.weight, self.out_proj.bias,
-            self.num_of_rows, self.num_of_col, float(ln_eps), cdt)
+            self.num_of_rows, self.num_of_col, float(ln_eps), cdt, row_index)
         if self.init_layer_scale is not None:
             out = out * self.gamma
         return out

@@ -4,8 +4,9 @@ models/mae/models_mamba_faster_mae_vimdecoder.py:515-950 (r
 Same constructor kwargs, ``state_dict`` keys and initialisation as the reference.  The encoder runs only the kept
 tokens through ``Mamba_masked`` mixers (fastvim_amd/mamba_simple_masked_faster.py); the decoder is the un-pooled Vim
 mixer over the full token grid (fastvim_amd/mamba_simple.py); both on the fused HIP kernels.  Host-side index
-bookkeeping (argsort of the masking noise, the odd-layer re-ordering of the kept tokens) stays in torch, as in the
-reference.
+bookkeeping (argsort of the masking noise, the odd-layer re-ordering of the kept tokens) is torch code, as in the
+reference, unless ``fused_tokens`` is set: then one launch per step computes all of it and the token copies are
+gather kernels (fastvim_amd/mae_tokens.py).
 
 One extension over the reference API: ``random_masking`` / ``forward`` / ``forward_encoder`` accept ``noise``
 (N, L) -- the per-token uniform scores whose argsort decides which tokens are kept -- so that a run can be
@@ -21,7 +22,7 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
-from . import losses, pixels
+from . import losses, mae_tokens, pixels
 from .fastvim import PatchEmbed, _compute_dtype, _init_weights, trunc_normal_
 from .layernorm import RMSNorm, layer_norm_fn
 from .mamba_simple_faster import linear_module
@@ -77,7 +78,10 @@ class Block_masked(nn.Module):
         i, j = indices.div(W, rounding_mode="floor"), indices % W
         return j * H + i
 
-    def forward(self, hidden_states: Tensor, residual: Optional[Tensor] = None, ids_keep=None, inference_params=None):
+    def forward(self, hidden_states: Tensor, residual: Optional[Tensor] = None, ids_keep=None, inference_params=None,
+                plan=None):
+        """``plan``: the step's ``TokenPlan`` (fastvim_amd/mae_tokens.py) -- the odd layers' order, its inverse and the
+        mixer's row index are read from it instead of being derived from ``ids_keep`` again; None: today's torch code."""
         cdt = _compute_dtype(hidden_states)
         is_rms = isinstance(self.norm, RMSNorm)
         if self.fused_add_norm:
@@ -91,6 +95,16 @@ class Block_masked(nn.Module):
             if self.residual_in_fp32:
                 residual = residual.to(torch.float32)
         rot = self.rotate_every_block is True and self.layer_idx % 2 != 0
+        if plan is not None:
+            if rot:
+                hidden_states = mae_tokens.gather_tokens(hidden_states, plan.order_index, plan.inverse_index)
+                hidden_states = self.mixer(hidden_states, plan.ids_keep_odd, inference_params=inference_params,
+                                           row_index=plan.row_index_odd)
+                hidden_states = mae_tokens.gather_tokens(hidden_states, plan.inverse_index, plan.order_index)
+            else:
+                hidden_states = self.mixer(hidden_states, plan.ids_keep, inference_params=inference_params,
+                                           row_index=plan.row_index_even)
+            return hidden_states, residual
         if rot:
             if self.rotate_indices.device != hidden_states.device:
                 self.rotate_indices = self.rotate_indices.to(hidden_states.device)
@@ -133,16 +147,22 @@ class MaskedAutoencoderViM(nn.Module):
     # Float images: True sends the loss through the fused kernel (fastvim_amd/losses.py), False keeps the eager
     # composition of ``forward_loss``.  uint8 images take the kernel either way.  A plain attribute: it may be set later.
     fused_loss = False
+    # True: the token bookkeeping -- the masking plan, the kept-token gather, the odd layers' permutes, the mixers' row indices,
+    # the decoder's input assembly -- runs on fastvim_amd/mae_tokens.py (one plan launch per step) where its predicate holds;
+    # False: the torch composition below.  Same values either way (``mask_token.grad`` up to its summation order).  A plain
+    # attribute: it may be set later.
+    fused_tokens = False
 
     def __init__(self, img_size=224, patch_size=16, stride=16, depth=24, embed_dim=192, decoder_embed_dim=512,
                  decoder_depth=2, norm_pix_loss=True, channels=3, ssm_cfg=None, drop_rate=0.0,
                  norm_epsilon: float = 1e-5, rms_norm: bool = False, initializer_cfg=None, fused_add_norm=False,
                  residual_in_fp32=False, device=None, dtype=None, init_layer_scale=None, use_norm_after_ssm=True,
                  embed_layer=PatchEmbed, scanpath_type="rowwise", rotate_every_block=True, collapse_method="mean",
-                 fused_loss=False, **kwargs):
+                 fused_loss=False, fused_tokens=False, **kwargs):
         factory_kwargs = {"device": device, "dtype": dtype}
         super().__init__()
         self.fused_loss = bool(fused_loss)
+        self.fused_tokens = bool(fused_tokens)
         self.residual_in_fp32 = residual_in_fp32
         self.fused_add_norm = fused_add_norm
         self.rotate_every_block = rotate_every_block
@@ -226,10 +246,22 @@ class MaskedAutoencoderViM(nn.Module):
     def random_masking(self, x, mask_ratio, noise=None):
         """Per-sample random masking by argsort of uniform noise; the kept ids are sorted ascending because the
         mixers are sequential (models_mamba_faster_mae_vimdecoder.py:738-772)."""
+        return self._masking(x, mask_ratio, noise)[:4]
+
+    def _masking(self, x, mask_ratio, noise=None):
+        """``random_masking`` plus the step's ``TokenPlan`` as a fifth value: None unless ``fused_tokens`` is set and
+        ``mae_tokens.mask_plan_ok`` holds (then the plan's launch replaces the index code and the gather is
+        ``gather_tokens``; same four values)."""
         N, L, D = x.shape
         len_keep = int(L * (1 - mask_ratio))
         if noise is None:
             noise = torch.rand(N, L, device=x.device)
+        if (self.fused_tokens and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and D % 4 == 0
+                and noise.device == x.device and tuple(noise.shape) == (N, L)
+                and mae_tokens.mask_plan_ok(noise, self.token_size, len_keep)):
+            plan = mae_tokens.mask_plan(noise, self.token_size, len_keep)
+            x_masked = mae_tokens.gather_tokens(x, plan.keep_index, plan.restore_index)
+            return x_masked, plan.mask, plan.ids_restore, plan.ids_keep, plan
         ids_shuffle = torch.argsort(noise, dim=1)          # ascend: small is keep, large is remove
         ids_shuffle[:, :len_keep] = ids_shuffle[:, :len_keep].sort().values
         ids_shuffle = ids_shuffle.contiguous()
@@ -239,7 +271,7 @@ class MaskedAutoencoderViM(nn.Module):
         mask = torch.ones([N, L], device=x.device)
         mask[:, :len_keep] = 0
         mask = torch.gather(mask, dim=1, index=ids_restore)   # 0 is keep, 1 is remove
-        return x_masked, mask, ids_restore, ids_keep
+        return x_masked, mask, ids_restore, ids_keep, None
 
     def _final_norm(self, norm, hidden_states, residual):
         is_rms = isinstance(norm, RMSNorm)
@@ -251,20 +283,38 @@ class MaskedAutoencoderViM(nn.Module):
                              residual_in_fp32=self.residual_in_fp32, is_rms_norm=is_rms)
 
     def forward_encoder(self, x, mask_ratio, inference_params=None, noise=None):
+        return self._encode(x, mask_ratio, inference_params, noise)[:3]
+
+    def _encode(self, x, mask_ratio, inference_params=None, noise=None):
+        """``forward_encoder`` plus the step's ``TokenPlan`` (or None) as a fourth value, for ``forward_decoder``."""
         x = self.patch_embed(x, self.pos_embed)
-        x, mask, ids_restore, ids_keep = self.random_masking(x, mask_ratio, noise)
+        if self.fused_tokens:
+            x, mask, ids_restore, ids_keep, plan = self._masking(x, mask_ratio, noise)
+        else:
+            (x, mask, ids_restore, ids_keep), plan = self.random_masking(x, mask_ratio, noise), None
         residual = None
         hidden_states = x
         for layer in self.layers:
-            hidden_states, residual = layer(hidden_states, residual, ids_keep.clone(), inference_params=inference_params)
-        return self._final_norm(self.norm_f, hidden_states, residual), mask, ids_restore
+            if plan is not None:
+                hidden_states, residual = layer(hidden_states, residual, inference_params=inference_params, plan=plan)
+            else:
+                hidden_states, residual = layer(hidden_states, residual, ids_keep.clone(), inference_params=inference_params)
+        return self._final_norm(self.norm_f, hidden_states, residual), mask, ids_restore, plan
 
-    def forward_decoder(self, x, ids_restore, inference_params=None):
+    def forward_decoder(self, x, ids_restore, inference_params=None, plan=None):
+        """``plan``: the ``TokenPlan`` that ``ids_restore`` came from -- the decoder's input is then assembled by
+        ``mae_tokens.decoder_tokens`` where it takes the tensors; None: the torch chain."""
         x = linear_module(self.decoder_embed, x)
+        if plan is not None and mae_tokens.decoder_tokens_ok(x, self.mask_token, self.decoder_pos_embed, plan):
+            x = mae_tokens.decoder_tokens(x, self.mask_token, self.decoder_pos_embed, plan)
+            return self._decode(x, inference_params)
         mask_tokens = self.mask_token.repeat(x.shape[0], ids_restore.shape[1] - x.shape[1], 1)
         x = torch.cat([x, mask_tokens.to(x.dtype)], dim=1)
         x = torch.gather(x, dim=1, index=ids_restore.unsqueeze(-1).repeat(1, 1, x.shape[2]))    # unshuffle
         x = x + self.decoder_pos_embed
+        return self._decode(x, inference_params)
+
+    def _decode(self, x, inference_params=None):
         residual = None
         for layer in self.decoder_blocks:
             x, residual = layer(x, residual, inference_params=inference_params)
@@ -300,8 +350,11 @@ class MaskedAutoencoderViM(nn.Module):
         """``imgs``: normalised float images, or a uint8 batch once ``fastvim_amd.pixels.attach_pixel_norm`` has put the
         normalisation table on the model: the patch embedding and the loss then look the pixels up inside their kernels."""
         table = pixels.pixel_table(self.patch_embed, imgs) if imgs.dtype == torch.uint8 else None
-        latent, mask, ids_restore = self.forward_encoder(imgs, mask_ratio, inference_params, noise=noise)
-        pred = self.forward_decoder(latent, ids_restore, inference_params)
+        latent, mask, ids_restore, plan = self._encode(imgs, mask_ratio, inference_params, noise=noise)
+        if plan is None:
+            pred = self.forward_decoder(latent, ids_restore, inference_params)
+        else:
+            pred = self.forward_decoder(latent, ids_restore, inference_params, plan=plan)
         if table is None and not self.fused_loss:
             loss = self.forward_loss(imgs, pred, mask)
         else:

@@ -72,7 +72,10 @@ const char* fv_last_error(void);
  *      Later, still 3: fv_random_erase, fv_patch_unfold_u8_re and fv_patch_unfold_mix_u8_re were ADDED (random erasing
  *      of the normalised image, with the boxes and the noise key in device memory); no existing entry point changed.
  *      Later, still 3: fv_mae_loss_ok, fv_mae_loss_fwd and fv_mae_loss_bwd were ADDED (the MAE reconstruction loss, from
- *      fp32 or uint8 images, fused into two launches forward and one backward); no existing entry point changed. */
+ *      fp32 or uint8 images, fused into two launches forward and one backward); no existing entry point changed.
+ *      Later, still 3: fv_mae_mask_plan, fv_tokens_gather, fv_mae_decoder_tokens_fwd and fv_mae_decoder_tokens_bwd were
+ *      ADDED (the MAE masking plan from one launch, the permuted token copies, the decoder's input assembly); no existing
+ *      entry point changed. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -981,6 +984,57 @@ int fv_mae_loss_fwd(const void* img, const float* table, const void* pred, int p
 int fv_mae_loss_bwd(const void* img, const float* table, const void* pred, int pred_dtype, const float* mask,
                     const float* row_stats, const float* sum_mask, const float* g, void* dpred, int batch, int height,
                     int width, int patch, fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * MAE token bookkeeping (csrc/mae_tokens.hip): the masking plan of a step from ONE launch, the permuted row copies that
+ * use it, and the decoder's input assembly.  B = batch, L = grid_h grid_w tokens, K = len_keep.
+ *
+ * fv_mae_mask_plan: one workgroup per sample.  noise (B, L) fp32.  rank[i] = #{j : noise[j] < noise[i], or equal and
+ *   j < i} -- the stable ascending order; the K lowest-ranked tokens are kept.  All outputs are written by this launch:
+ *   ids_keep        (B, K) int64   positions of the kept tokens, ascending
+ *   ids_restore     (B, L) int64   kept token: its place among the kept ones; removed token: its rank
+ *   mask            (B, L) fp32    1 = removed
+ *   keep_index      (B, K) int32   = ids_keep
+ *   restore_index   (B, L) int32   = ids_restore where < K, else -1
+ *   row_index_even  (2, B, K) int32  [r, (grid_h - 1) - flip(r)], r = ids_keep / grid_w
+ *   ids_keep_odd    (B, K) int64   the kept tokens' places (id % grid_w) grid_h + id / grid_w in the transposed grid, ascending
+ *   order, inverse  (B, K) int64   ids_keep_odd[q] is the transposed place of kept token order[q]; inverse[order[q]] = q
+ *   order_index, inverse_index  (B, K) int32  the same two
+ *   row_index_odd   (2, B, K) int32  [r, (grid_w - 1) - flip(r)], r = ids_keep_odd / grid_h
+ *   L <= FV_MAE_PLAN_MAX_TOKENS, 1 <= K <= L.  Finite noise is the contract.  The order is taken on the bit patterns
+ *   (-0 == +0), so ANY input, NaN included, gives a permutation: every index written is in range and nothing is written
+ *   outside the outputs; which tokens a NaN makes kept is unspecified.
+ *
+ * fv_tokens_gather: out[b, t, :] = in[b, index[b, t], :] for in (B, len_in, dim), index (B, len_out) int32, out
+ *   (B, len_out, dim); an index outside [0, len_in) writes a zero row.  in / out: fp32 or bf16 each; the same type is a
+ *   bit copy, different types one conversion (round to nearest even).  dim % 4 == 0.  With unique indices the adjoint is
+ *   the gather by the inverse index, -1 where a row of `in` was not picked.
+ *
+ * fv_mae_decoder_tokens_fwd: out[b, l, :] = (r >= 0 ? x[b, r, :] : mask_token rounded to x_dtype) + pos_embed[l, :] with
+ *   r = restore_index[b, l]; x (B, K, dim) fp32 or bf16, mask_token (dim) fp32, pos_embed (L, dim) fp32, out (B, L, dim)
+ *   fp32: one fp32 rounding, of the sum.  dim % 4 == 0.
+ * fv_mae_decoder_tokens_bwd: two launches.  dx[b, r, :] = dout[b, l, :] in x_dtype for the rows with r >= 0;
+ *   dmask_token (dim) fp32 = the sum of the other rows of dout (B, L, dim) fp32, each rounded to x_dtype first, added in
+ *   fp64 in a fixed order: a workgroup per FV_MAE_DECODER_ROWS_PER_BLOCK rows of (B L) writes one row of `partials`
+ *   (n_partials = ceil(B L / FV_MAE_DECODER_ROWS_PER_BLOCK) rows of dim doubles, caller-allocated), a second launch adds
+ *   those.  No atomics: the same inputs give the same bits.  restore_index must hold each of 0 .. K-1 once per sample (as
+ *   fv_mae_mask_plan writes it) for every row of dx to be written.
+ * Alignment: every buffer that of its element type only.
+ * ---------------------------------------------------------------------- */
+#define FV_MAE_PLAN_MAX_TOKENS 1024
+#define FV_MAE_DECODER_ROWS_PER_BLOCK 32
+int fv_mae_mask_plan(const float* noise, long long* ids_keep, long long* ids_restore, float* mask, int* keep_index,
+                     int* restore_index, int* row_index_even, long long* ids_keep_odd, long long* order, long long* inverse,
+                     int* order_index, int* inverse_index, int* row_index_odd, int batch, int grid_h, int grid_w,
+                     int len_keep, fv_stream_t stream);
+int fv_tokens_gather(const void* in, int in_dtype, const int* index, void* out, int out_dtype, int batch, int len_in,
+                     int len_out, int dim, fv_stream_t stream);
+int fv_mae_decoder_tokens_fwd(const void* x, int x_dtype, const float* mask_token, const float* pos_embed,
+                              const int* restore_index, float* out, int batch, int len, int len_keep, int dim,
+                              fv_stream_t stream);
+int fv_mae_decoder_tokens_bwd(const float* dout, const int* restore_index, void* dx, int x_dtype, double* partials,
+                              int n_partials, float* dmask_token, int batch, int len, int len_keep, int dim,
+                              fv_stream_t stream);
 
 #ifdef __cplusplus
 }
