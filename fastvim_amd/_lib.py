@@ -31,6 +31,7 @@ C_ABI_SYMBOLS = (
     "fv_grad_sumsq_blocks", "fv_grad_sumsq_partials", "fv_adamw_flat_groups",
     "fv_pack_weight_frags_batched", "fv_mixer_conv_pool_bwd_dgrad_pk", "fv_mixer_combine_out_proj_addnorm_pk",
     "fv_pack_weight_frags_w2_batched", "fv_mixer_conv_pool_bwd_dgrad_pk2",
+    "fv_pack_weight_frags_in_batched", "fv_gemm_bf16_inproj_pk",
     "fv_mix_batch", "fv_patch_unfold_mix", "fv_mixup_target", "fv_label_ce",
     "fv_patch_unfold_chan", "fv_chan_embed_table", "fv_chan_embed_scatter",
     "fv_mixer_plan",

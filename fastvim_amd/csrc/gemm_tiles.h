@@ -312,6 +312,116 @@ __device__ __forceinline__ void tile_times_w2_rows(const char* tile, char* ldsB,
   }
 }
 
+// C (64 tile rows, N columns) = T @ W^T in passes of 384 columns: T = the workgroup's 64 x 192 bf16 tile in LDS (rows RS bytes
+// apart, already published to all four waves), W (N, 192) given as its fragment-major copy (fv_pack_weight_frags_in_batched) --
+// 16-byte unit (((p * 4 + wv) * 6 + ks) * 6 + nb) * 64 + lane = W[384 p + 96 wv + 16 nb + (lane & 15)][32 ks + 8 (lane >> 4) .. + 8).
+// Pass p: wave wv owns columns [384 p + 96 wv, + 96) and all 64 rows; its 36 KiB of the pass is one contiguous run that goes
+// from L2 straight into operand registers, 1 KiB per load, through a ring of three k steps that keeps running across the
+// pass boundary (the next pass's first fragments are requested before this pass's C leaves).  No LDS weight stage, no
+// barrier, no wait for the stores.  C leaves through the wave's slab (16 rows x 208 B), three 16-byte stores per lane and
+// round.  rowof(tile row) = row of C, or -1 for a row that is not stored.  Same MFMA, operand order, k order and single
+// accumulator per element as gemm_bf16_body: bit-identical to fv_gemm_bf16.
+#ifndef TPW_SLAB_ROWS
+#define TPW_SLAB_ROWS 16     // tile rows per slab round (16 or 32): three or six 16-byte stores per lane and round
+#endif
+#ifndef TPW_DBG
+#define TPW_DBG 0            // phase probes (tuning): 1 C is not stored, 2 no weight stream (the MFMAs run on zero fragments)
+#endif
+constexpr int TPW_K = 192, TPW_KS = TPW_K / 32, TPW_NB = 6, TPW_RING = 3;
+constexpr int TPW_SLAB_RS = TPW_NB * 32 + 16, TPW_SLAB = TPW_SLAB_ROWS * TPW_SLAB_RS;      // = 4 r (mod 64) dwords over 16 rows: conflict-free
+static_assert(TPW_SLAB_ROWS == 16 || TPW_SLAB_ROWS == 32, "slab rounds of 16 or 32 tile rows");
+constexpr int TPW_WAVE_B = TPW_KS * TPW_NB * 1024, TPW_PASS_B = 4 * TPW_WAVE_B;
+// The wave's weight stream and the ring its fragments wait in.  prefill() requests the first three k steps of pass0: call it as early
+// as the tile's producer allows (in front of the barrier that publishes the tile), so they arrive under it.
+struct TpwRing {
+  bf16x8 wf[TPW_RING][TPW_NB];
+  const char* wbase;      // (uniform) the wave's first fragment (+ pass * TPW_PASS_B + fragment * 1024 + loff)
+  uint32_t loff;          // this lane's 16 bytes of a fragment
+  __device__ __forceinline__ void prefill(const bf16_t* Wpk, int wv, int lane, int pass0 = 0) {
+    wbase = reinterpret_cast<const char*>(Wpk) + (long)wv * TPW_WAVE_B;
+    loff = (uint32_t)lane * 16;
+    const char* wp = wbase + (long)pass0 * TPW_PASS_B;
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < TPW_RING; ++s)
+#pragma unroll
+      for (int a = 0; a < TPW_NB; ++a) {
+        if constexpr (TPW_DBG == 2) wf[s][a] = bf16x8{};
+        else wf[s][a] = *reinterpret_cast<const bf16x8*>(wp + (s * TPW_NB + a) * 1024 + loff);
+      }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+};
+// NPASS passes, [pass0, pass0 + NPASS), fully unrolled: the ring (prefilled for pass0) is refilled three steps ahead
+// straight through the pass boundaries, and every wait is a counted one.
+template <int RS, int NPASS, class RowOf>
+__device__ __forceinline__ void tile_times_packed_w(const char* tile, char* slab, TpwRing& ring, int pass0, bf16_t* C,
+                                                    long ldc, RowOf rowof, int wv, int lane) {
+  constexpr int STEPS = NPASS * TPW_KS;
+  auto& wf = ring.wf;
+  const char* wp = ring.wbase + (long)pass0 * TPW_PASS_B;
+  const uint32_t loff = ring.loff;
+  const char* afrag = tile + (lane & 15) * RS + (lane >> 4) * 16;
+  f32x4 acc[TPW_NB][4];
+  static_for<STEPS>([&](auto s_c) {
+    constexpr int s = decltype(s_c)::value, ks = s % TPW_KS, pass = s / TPW_KS;
+    if constexpr (ks == 0) {
+#pragma unroll
+      for (int a = 0; a < TPW_NB; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    bf16x8 cur[TPW_NB];
+#pragma unroll
+    for (int a = 0; a < TPW_NB; ++a) cur[a] = wf[s % TPW_RING][a];
+    if constexpr (s + TPW_RING < STEPS && TPW_DBG != 2) {
+      constexpr int t = s + TPW_RING, off = (t / TPW_KS) * TPW_PASS_B + (t % TPW_KS) * TPW_NB * 1024;
+#pragma unroll
+      for (int a = 0; a < TPW_NB; ++a) wf[s % TPW_RING][a] = *reinterpret_cast<const bf16x8*>(wp + off + a * 1024 + loff);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    bf16x8 fa[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) fa[b] = *reinterpret_cast<const bf16x8*>(afrag + b * 16 * RS + ks * 64);
+#pragma unroll
+    for (int a = 0; a < TPW_NB; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur[a], fa[b], acc[a][b], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (ks == TPW_KS - 1) {
+      // bf16 through the wave's slab: 16-byte stores, a row's 96 columns as one run
+      //      acc[a][b][j] = C[tile row b * 16 + (lane & 15)][384 pass + 96 wv + 16 a + (lane >> 4) * 4 + j]
+      constexpr int CH = TPW_NB * 2;
+      // (the store addresses are made from a lane index the compiler cannot see through: shared between the passes they
+      //  would sit in two dozen registers across the next K loop, which has none to spare)
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      constexpr int RB = TPW_SLAB_ROWS / 16;
+#pragma unroll
+      for (int h = 0; h < 4 / RB; ++h) {
+#pragma unroll
+        for (int bb = 0; bb < RB; ++bb)
+#pragma unroll
+          for (int a = 0; a < TPW_NB; ++a) {
+            const f32x4 v = acc[a][h * RB + bb];
+            uint2 pk = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+            *reinterpret_cast<uint2*>(slab + (bb * 16 + (ln & 15)) * TPW_SLAB_RS + (a * 16 + (ln >> 4) * 4) * 2) = pk;
+          }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int i = 0; i < TPW_SLAB_ROWS * CH / 64; ++i) {
+          const int idx = i * 64 + ln, r = idx / CH, ch = idx - r * CH;
+          const long m = rowof(h * TPW_SLAB_ROWS + r);
+          const int n = (pass0 + pass) * 384 + wv * 96 + ch * 8;
+          if (TPW_DBG == 1 ? m == -2 : m >= 0)
+            *reinterpret_cast<u32x4*>(C + m * ldc + n) = *reinterpret_cast<const u32x4*>(slab + r * TPW_SLAB_RS + ch * 16);
+        }
+        __builtin_amdgcn_wave_barrier();
+      }
+    }
+  });
+}
+
 template <int BMT, int RSB, int WMODE>
 __device__ __forceinline__ void tile_times_w2(const char* tile, char* ldsB, char* slabs, const bf16_t* W2, long ldw2, int N2,
                                               bf16_t* C2, int m0, int M, int tid) {

@@ -530,6 +530,26 @@ __global__ __launch_bounds__(256) void pack_weight_frags_w2_kernel(PackJobsW2 J)
   J.dst[blockIdx.y][u] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// Fragment-major copies of up to 64 weights (N, 192), K-contiguous, N a multiple of 384, for the forward product in which the
+// weight's rows are output columns dealt 96 per wave and 384 per pass (in_proj.weight in fv_gemm_bf16_inproj_pk): the
+// 16-byte unit
+//   u = (((p * 4 + wv) * 6 + ks) * 6 + nb) * 64 + lane   holds   src[384 p + 96 wv + 16 nb + (lane & 15)][32 ks + 8 (lane >> 4) .. + 8)
+// (fastvim_amd.mixer_ops.pack_index_in is the same map).  A thread moves one unit: the writes are contiguous, the reads
+// 16-byte pieces of 16 rows.
+constexpr int PKIN_K = 192;
+struct PackJobsIn {
+  const uint4* src[TRJ_MAX];
+  uint4* dst[TRJ_MAX];
+  int units;     // N * 192 / 8
+};
+__global__ __launch_bounds__(256) void pack_weight_frags_in_kernel(PackJobsIn J) {
+  const int u = blockIdx.x * 256 + threadIdx.x;
+  if (u >= J.units) return;
+  const int lane = u & 63, t = u >> 6, nb = t % 6, ks = (t / 6) % 6, wv = (t / 36) & 3, p = t / 144;
+  const int row = 384 * p + 96 * wv + 16 * nb + (lane & 15), unit_in_row = 4 * ks + (lane >> 4);
+  J.dst[blockIdx.y][u] = J.src[blockIdx.y][row * (PKIN_K / 8) + unit_in_row];
+}
+
 // Bytes per tile store of the even-width unfold forms.  Chunks of `gjc` patches start at patch (b*gh + gi)*gw + k*gjc and
 // hold gjc or gw - k*gjc patches: every start and length is a multiple of gcd(gw, gjc) patches of `patch_bytes` each
 // (a multiple of 4: the width is even, an element at least 2 bytes), and `out` itself is 16-byte aligned.
@@ -809,6 +829,24 @@ extern "C" int fv_pack_weight_frags_w2_batched(const void* const* srcs, void* co
     J.dst[j] = (uint4*)dsts[j];
   }
   hipLaunchKernelGGL(pack_weight_frags_w2_kernel, dim3(fv_cdiv(PKW2_UNITS, 256), njobs), dim3(256), 0, (hipStream_t)stream, J);
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
+// dsts[j] = the fragment-major copy of srcs[j] ((N, 192) bf16 row-major, N a multiple of 384) that fv_gemm_bf16_inproj_pk
+// streams
+extern "C" int fv_pack_weight_frags_in_batched(const void* const* srcs, void* const* dsts, int njobs, int N, fv_stream_t stream) {
+  FV_CHECK(srcs && dsts && njobs > 0 && njobs <= TRJ_MAX, "pack_weight_frags_in_batched: 1..%d jobs", TRJ_MAX);
+  FV_CHECK(N > 0 && N % 384 == 0 && N <= (1 << 20), "pack_weight_frags_in_batched: N = %d is not a multiple of 384", N);
+  PackJobsIn J{};
+  for (int j = 0; j < njobs; ++j) {
+    FV_CHECK(srcs[j] && dsts[j] && srcs[j] != dsts[j], "pack_weight_frags_in_batched: null or aliased pointer in job %d", j);
+    FV_CHECK(((uintptr_t)srcs[j] & 15) == 0 && ((uintptr_t)dsts[j] & 15) == 0, "pack_weight_frags_in_batched: job %d is not 16-byte aligned", j);
+    J.src[j] = (const uint4*)srcs[j];
+    J.dst[j] = (uint4*)dsts[j];
+  }
+  J.units = N * (PKIN_K / 8);
+  hipLaunchKernelGGL(pack_weight_frags_in_kernel, dim3(fv_cdiv(J.units, 256), njobs), dim3(256), 0, (hipStream_t)stream, J);
   FV_LAUNCH_CHECK();
   return FV_OK;
 }

@@ -43,7 +43,7 @@ def _drop_derived_shadows(model):
     not catch them)."""
     for p in model.parameters():
         for a in ("_fv_shadow_t", "_fv_shadow_t_version", "_fv_shadow_pk", "_fv_shadow_pk_version",
-                  "_fv_shadow_pk2", "_fv_shadow_pk2_version"):
+                  "_fv_shadow_pk2", "_fv_shadow_pk2_version", "_fv_shadow_pk_in", "_fv_shadow_pk_in_version"):
             if hasattr(p, a):
                 delattr(p, a)
     for mod in model.modules():
@@ -191,7 +191,21 @@ class FlatTrainingState:
             self._pk2_src.append(src)
             self._pk2_dst.append(pk2)
             self._pk2_params.append(w)
-        self._pk_dst = self._pk_jobs[768][1] + self._pk_jobs[384][1] + self._pk2_dst
+        # ... and of the in_proj shadows (N, 192) as stored, as the operand of their forward product (mixer_ops.pack_index_in;
+        # fv_gemm_bf16_inproj_pk): one more launch, straight from the plain shadow
+        self._pkin_src, self._pkin_dst, self._pkin_params = [], [], []
+        if shadow_dtype == torch.bfloat16 and dev.type == "cuda":
+            for mod in mixers.values():
+                w = mod.in_proj.weight
+                if (w.dim() == 2 and w.shape[1] == 192 and w.shape[0] % 384 == 0 and w.requires_grad
+                        and getattr(w, "_fv_shadow", None) is not None and (not self._pkin_src or w.shape == self._pkin_src[0].shape)):
+                    pk = torch.empty(w.numel(), device=dev, dtype=shadow_dtype)
+                    w._fv_shadow_pk_in = pk
+                    w._fv_shadow_pk_in_version = -1
+                    self._pkin_src.append(w._fv_shadow)
+                    self._pkin_dst.append(pk)
+                    self._pkin_params.append(w)
+        self._pk_dst = self._pk_jobs[768][1] + self._pk_jobs[384][1] + self._pk2_dst + self._pkin_dst
         # ... and of the x_proj weight pairs of the wide models (d_inner >= 768), (2, W, d_inner) -> (2, d_inner, W): the
         # x_proj adjoint's data half streams them K-contiguous into the bf16 matrix cores (fv_mixer_xproj_bwd3)
         self._tx_src, self._tx_dst, self._tx_params = [], [], []
@@ -297,7 +311,7 @@ class FlatTrainingState:
         """Re-make the transposed in_proj shadows from ``shadow_flat`` (one launch) and then the fragment-major copies of
         them and of the out_proj shadows (one launch per shape and operand role); called after every shadow refresh: here
         and by the fused optimizer step."""
-        from .mixer_ops import pack_weight_frags, pack_weight_frags_w2, transpose_bf16_batched
+        from .mixer_ops import pack_weight_frags, pack_weight_frags_in, pack_weight_frags_w2, transpose_bf16_batched
         for src, dst, params in ((self._t_src, self._t_dst, self._t_params),
                                  (getattr(self, "_tx_src", []), getattr(self, "_tx_dst", []), getattr(self, "_tx_params", []))):
             if src:
@@ -313,6 +327,10 @@ class FlatTrainingState:
             pack_weight_frags_w2(self._pk2_src, self._pk2_dst)
             for p in self._pk2_params:
                 p._fv_shadow_pk2_version = p._version
+        if getattr(self, "_pkin_src", []):
+            pack_weight_frags_in(self._pkin_src, self._pkin_dst)
+            for p in self._pkin_params:
+                p._fv_shadow_pk_in_version = p._version
 
     @property
     def world_size(self):

@@ -69,7 +69,8 @@ def _shadow_pk(w, cdt, plain, attr="_fv_shadow_pk", pack=None):
     ``_shadow`` of the same weight, already refreshed): an in-place write to the parameter since the state last re-made the
     copy (version counter) is caught here and the copy re-packed from it, like ``_shadow_t``.  ``attr`` / ``pack``: which
     copy and its pack launch -- ``_fv_shadow_pk2`` / ``M.pack_weight_frags_w2`` for out_proj.weight as the operand of its data
-    gradient (``mixer_ops.pack_index_w2``)."""
+    gradient (``mixer_ops.pack_index_w2``), ``_fv_shadow_pk_in`` / ``M.pack_weight_frags_in`` for in_proj.weight as the operand
+    of its forward product (``mixer_ops.pack_index_in``)."""
     pk = getattr(w, attr, None)
     if pk is None or pk.dtype != cdt or not _PackedWeights.enabled:
         return None
@@ -143,6 +144,17 @@ def linear_fwd(a2, w_c, bias=None):
     if _any_ok(a2, w_c):
         return gemm_any_nt(a2, w_c, bias)
     return F.linear(a2, w_c, None if bias is None else bias.to(a2.dtype))      # fp16 / fp64 / CPU callers of the op-level API
+
+
+def in_proj_fwd(a2, W_in, W_in_c, b_in, cdt):
+    """The mixer's in_proj: a2 (M, d) @ W_in_c (2 d_in, d)^T (+ b_in).  With d = 192, no bias, a contiguous bf16 ``a2`` and the
+    fragment-major copy a flat training state keeps on ``W_in`` (``mixer_ops.pack_index_in``), the launch that streams that copy
+    (fv_gemm_bf16_inproj_pk); ``linear_fwd`` for everything else.  Same bits either way."""
+    if b_in is None and M.in_proj_pk_ok(a2, W_in.shape[0]):
+        W_in_pk = _shadow_pk(W_in, cdt, W_in_c, "_fv_shadow_pk_in", M.pack_weight_frags_in)
+        if W_in_pk is not None:
+            return M.in_proj_fwd_pk(a2, W_in_pk, W_in.shape[0])
+    return linear_fwd(a2, W_in_c, b_in)
 
 
 def linear_dgrad(g2, w_c):
@@ -622,7 +634,7 @@ class FastVimMixerFn(torch.autograd.Function):
             W_out_c = _shadow(W_out, cdt) if W_out is not None else None
             xz = getattr(ctx, "precomputed_xz", None)          # ChainedBlockFn: in_proj ran inside the previous launch
             if xz is None:
-                xz = linear_fwd(h_c.view(B * Ltok, d), W_in_c, b_in)
+                xz = in_proj_fwd(h_c.view(B * Ltok, d), W_in, W_in_c, b_in, cdt)
             xz = xz.view(B, Ltok, 2 * d_in)                                                # (B, L, 2 d_in)
             cw2, cwb2 = cw.reshape(d_in, -1), cw_b.reshape(d_in, -1)
             amax = None

@@ -532,6 +532,68 @@ def pack_weight_frags_w2(srcs, dsts):
         L.check(lib.fv_pack_weight_frags_w2_batched(ins, outs, L.i32(k), L.stream_of(a[0])), "pack_weight_frags_w2_batched")
 
 
+PACK_IN_K = 192     # reduction length of the forward product whose weight rows are dealt 96 per wave and 384 per pass
+
+
+def pack_index_in(N):
+    """The fragment-major layout of ``in_proj.weight`` (N, 192), N a multiple of 384, as the operand of its FORWARD product
+    (fv_gemm_bf16_inproj_pk: the weight's rows are output columns), as a gather: a (N * 192 / 8, 2) int64 tensor whose row
+    ``u`` is (row, first column) of the 8-element, 16-byte unit that packed unit ``u`` holds:
+    u = (((p * 4 + wv) * 6 + ks) * 6 + nb) * 64 + lane   holds   W[384 p + 96 wv + 16 nb + (lane & 15)][32 ks + 8 (lane >> 4) .. + 8)
+    -- the MFMA operand that lane loads for column block ``nb`` at k step ``ks`` of pass ``p`` in wave ``wv``."""
+    assert N > 0 and N % 384 == 0
+    u = torch.arange(N * PACK_IN_K // 8)
+    lane, t = u % 64, u // 64
+    nb, ks, wv, p = t % 6, (t // 6) % 6, (t // 36) % 4, t // 144
+    return torch.stack([384 * p + 96 * wv + 16 * nb + (lane % 16), 32 * ks + 8 * (lane // 16)], dim=1)
+
+
+def pack_weight_frags_in_ref(W):
+    """``pack_index_in`` applied with torch indexing (any device): the definition ``pack_weight_frags_in`` is tested against."""
+    N, K = W.shape
+    assert K == PACK_IN_K
+    idx = pack_index_in(N).to(W.device)
+    cols = idx[:, 1:2] + torch.arange(8, device=W.device)
+    return W[idx[:, 0:1], cols].reshape(N, K)
+
+
+def pack_weight_frags_in(srcs, dsts):
+    """dsts[j] = ``pack_index_in`` copy of srcs[j] ((N, 192) bf16 contiguous, N a multiple of 384), one launch per 64 weights
+    (fv_pack_weight_frags_in_batched)."""
+    lib = L.lib()
+    N, K = srcs[0].shape
+    assert K == PACK_IN_K and N % 384 == 0
+    for lo in range(0, len(srcs), 64):
+        a, b = srcs[lo:lo + 64], dsts[lo:lo + 64]
+        assert all(t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (N, K) for t in a)
+        assert all(t.dtype == torch.bfloat16 and t.is_contiguous() and t.numel() == N * K for t in b)
+        k = len(a)
+        ins = (ctypes.c_void_p * k)(*[t.data_ptr() for t in a])
+        outs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in b])
+        L.check(lib.fv_pack_weight_frags_in_batched(ins, outs, L.i32(k), L.i32(N), L.stream_of(a[0])), "pack_weight_frags_in_batched")
+
+
+def in_proj_pk_ok(a2, N):
+    """Does ``in_proj_fwd_pk`` take this A (M, K) and output width?  K = 192, N a multiple of 384, bf16, A contiguous
+    (lda == K) and 16-byte aligned."""
+    return (a2.is_cuda and a2.dtype == torch.bfloat16 and a2.dim() == 2 and a2.shape[1] == PACK_IN_K and a2.shape[0] > 0
+            and N > 0 and N % 384 == 0 and a2.is_contiguous() and a2.data_ptr() % 16 == 0)
+
+
+def in_proj_fwd_pk(a2, W_pk, N, rows_per_tile=0):
+    """a2 (M, 192) @ W (N, 192)^T -> (M, N) bf16 with ``W_pk`` the ``pack_index_in`` copy of W: bit-identical to
+    ``gemm_nt(a2, W)`` (fv_gemm_bf16_inproj_pk).  ``rows_per_tile``: 0 the library's choice, 1..64 rows of the output per
+    workgroup, -1 the rows dealt evenly over whole rounds of resident workgroups.  Anything ``in_proj_pk_ok`` refuses is an
+    error here: callers take ``gemm_nt``."""
+    M_, K = a2.shape
+    assert W_pk.dtype == torch.bfloat16 and W_pk.is_contiguous() and W_pk.numel() == N * K
+    c = torch.empty(M_, N, device=a2.device, dtype=torch.bfloat16)
+    L.check(L.lib().fv_gemm_bf16_inproj_pk(L.ptr(a2), L.ptr(W_pk), L.ptr(c), L.i32(M_), L.i32(N), L.i32(K),
+                                           ctypes.c_long(a2.stride(0)), L.i32(rows_per_tile), L.stream_of(a2)),
+            "gemm_bf16_inproj_pk")
+    return c
+
+
 XPROJ_WIDTHS = (44, 56, 80, 96, 112, 34, 36, 38, 64)
 
 

@@ -75,7 +75,9 @@ const char* fv_last_error(void);
  *      fp32 or uint8 images, fused into two launches forward and one backward); no existing entry point changed.
  *      Later, still 3: fv_mae_mask_plan, fv_tokens_gather, fv_mae_decoder_tokens_fwd and fv_mae_decoder_tokens_bwd were
  *      ADDED (the MAE masking plan from one launch, the permuted token copies, the decoder's input assembly); no existing
- *      entry point changed. */
+ *      entry point changed.
+ *      Later, still 3: fv_pack_weight_frags_in_batched and fv_gemm_bf16_inproj_pk were ADDED (in_proj forward at
+ *      d_model 192 with its weight streamed in MFMA fragment order); fv_gemm_bf16 is unchanged. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -576,6 +578,22 @@ int fv_pack_weight_frags_batched(const void* const* srcs, void* const* dsts, int
  * (wv 0..3, ks 0..5, nb 0..5, lane 0..63) -- the MFMA operand lane `lane` of wave wv feeds for column block nb at k step
  * ks in the second phase of fv_mixer_conv_pool_bwd_dgrad_pk2.  dsts 16-byte aligned, no aliasing. */
 int fv_pack_weight_frags_w2_batched(const void* const* srcs, void* const* dsts, int njobs, fv_stream_t stream);
+
+/* Fragment-major copies of up to 64 weights (N, 192) bf16 row-major, N a multiple of 384, whose rows are OUTPUT COLUMNS of a
+ * forward product (in_proj.weight), in one launch; dsts[j] holds the same elements in 16-byte units:
+ *   unit (((p * 4 + wv) * 6 + ks) * 6 + nb) * 64 + lane  =  srcs[j][384 p + 96 wv + 16 nb + (lane & 15)][32 ks + 8 (lane >> 4) .. + 8)
+ * (p 0..N/384-1, wv 0..3, ks 0..5, nb 0..5, lane 0..63) -- the MFMA operand lane `lane` of wave wv loads for column block nb
+ * at k step ks of pass p in fv_gemm_bf16_inproj_pk.  Both sides 16-byte aligned, no aliasing. */
+int fv_pack_weight_frags_in_batched(const void* const* srcs, void* const* dsts, int njobs, int N, fv_stream_t stream);
+
+/* C (M, N) bf16 contiguous = A (M, 192) bf16 @ W^T with W (N, 192) given as W_pk, its fragment-major copy
+ * (fv_pack_weight_frags_in_batched): one workgroup per tile of up to 64 rows, the tile in LDS, the weight streamed from L2
+ * into MFMA operand registers.  Built for K == 192, N % 384 == 0, lda == K, 16-byte aligned operands, no bias: anything
+ * else is an error (callers take fv_gemm_bf16).  rows_per_tile: 0 = the library's choice, 1..64 = rows of C per workgroup,
+ * -1 = the rows dealt evenly over whole rounds of 2 x CU-count workgroups.  Same MFMA, operand order and k order as
+ * fv_gemm_bf16: C is bit-identical to it, whatever rows_per_tile. */
+int fv_gemm_bf16_inproj_pk(const void* A, const void* W_pk, void* C, int M, int N, int K, long lda, int rows_per_tile,
+                           fv_stream_t stream);
 
 /* fv_gemm_bf16_addnorm with a second GEMM phase: C2 (M, N2) bf16 = y @ W2^T, W2 (N2, N) bf16 row-major -- the block's
  * in_proj (mamba_simple_faster.py:189-193) computed from the normalised tile while it is still in LDS; bit-identical to
