@@ -77,7 +77,10 @@ const char* fv_last_error(void);
  *      ADDED (the MAE masking plan from one launch, the permuted token copies, the decoder's input assembly); no existing
  *      entry point changed.
  *      Later, still 3: fv_pack_weight_frags_in_batched and fv_gemm_bf16_inproj_pk were ADDED (in_proj forward at
- *      d_model 192 with its weight streamed in MFMA fragment order); fv_gemm_bf16 is unchanged. */
+ *      d_model 192 with its weight streamed in MFMA fragment order); fv_gemm_bf16 is unchanged.
+ *      Later, still 3: fv_resample_u8_ok, fv_resample_workspace_ints, fv_resample_coeffs and fv_resample_u8 were ADDED
+ *      (bicubic resize, crop window and flip of uint8 images on the device, bit-exact to PIL); no existing entry point
+ *      changed. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -1053,6 +1056,46 @@ int fv_mae_decoder_tokens_fwd(const void* x, int x_dtype, const float* mask_toke
 int fv_mae_decoder_tokens_bwd(const float* dout, const int* restore_index, void* dx, int x_dtype, double* partials,
                               int n_partials, float* dmask_token, int batch, int len, int len_keep, int dim,
                               fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Device-side geometry of the uint8 loaders: bicubic resize, crop window and horizontal flip of decoded 8-bit images,
+ * bit for bit what PIL's `Image.resize(size, BICUBIC)` (ImagingResample, 8 bits per channel: horizontal pass, uint8
+ * intermediate, vertical pass, integer coefficients of 22 fraction bits) followed by a crop and a flip computes --
+ * the reference's RandomResizedCropAndInterpolation + RandomHorizontalFlip (mae/datasets_mae.py:83-99) and its
+ * Resize + CenterCrop (datasets_supervised.py:254-262), in front of ToTensor / Normalize (fv_patch_unfold_u8).
+ *
+ *   pool   uint8, `pool_bytes` long: the decoded sources back to back, each H x W x 3 interleaved with packed rows
+ *          (PIL's / numpy's layout); a source may start at ANY byte (rows of 3 w_src bytes have every alignment anyway).
+ *   plan   (batch, FV_RESAMPLE_PLAN_INTS) int32 in DEVICE memory, read when the kernels RUN (a replayed graph takes the
+ *          plan and the pool contents of that moment).  Per sample:
+ *            [0] [1]  byte offset of the source in the pool, low and high 32 bits
+ *            [2] [3]  h_src, w_src
+ *            [4] [5]  o_h, o_w: the FULL output size of the resize
+ *            [6] [7]  win_y, win_x: origin of the s_h x s_w window of it that is written
+ *            [8]      flip != 0: out[.., x] = resized[.., win_x + s_w - 1 - x]
+ *            [9..11]  unused, 0
+ *   ws     int32 workspace of fv_resample_workspace_ints(batch, s_h, s_w) words, 4-byte aligned: per sample the x axis
+ *          then the y axis, each (2 + FV_RESAMPLE_MAX_TAPS) rows of S words -- lo[S], cnt[S], then c[k][i].
+ *   out    (batch, 3, s_h, s_w) uint8, planar, contiguous; any alignment (4-byte stores when it allows them).
+ *
+ * fv_resample_coeffs: one launch, a workgroup per (sample, axis): the window's filter bounds and integer coefficients
+ *   in fp64 without contraction or fast-math -- PIL's precompute_coeffs + normalize_coeffs_8bpc.  A plan row that
+ *   fv_resample_u8_ok refuses, or whose source does not lie inside the pool, gets cnt = 0 everywhere: the main launch
+ *   then reads nothing of that sample and writes zeros.  (Callers check on the host first: fastvim_amd/resample.py.)
+ * fv_resample_u8: one launch over (column tile, band of FV_RESAMPLE_BAND rows, sample); reads what fv_resample_coeffs
+ *   wrote for the SAME plan, pool size and window size.  No atomics; the same inputs give the same bits.
+ * fv_resample_u8_ok: host code, the range both serve -- batch in [1, 4096], s_h and s_w in [8, 1024], h_src and w_src
+ *   in [1, 16384], o_h and o_w up to 65536, the window inside the output, and at most FV_RESAMPLE_MAX_TAPS filter taps
+ *   per axis: h_src <= 16 o_h and w_src <= 16 o_w.
+ * ---------------------------------------------------------------------- */
+#define FV_RESAMPLE_PLAN_INTS 12
+#define FV_RESAMPLE_MAX_TAPS 65
+#define FV_RESAMPLE_BAND 16
+int fv_resample_u8_ok(int batch, int s_h, int s_w, int h_src, int w_src, int o_h, int o_w, int win_y, int win_x);
+long long fv_resample_workspace_ints(int batch, int s_h, int s_w);
+int fv_resample_coeffs(const int* plan, long long pool_bytes, int* ws, int batch, int s_h, int s_w, fv_stream_t stream);
+int fv_resample_u8(const void* pool, long long pool_bytes, const int* plan, const int* ws, void* out, int batch, int s_h,
+                   int s_w, fv_stream_t stream);
 
 #ifdef __cplusplus
 }
