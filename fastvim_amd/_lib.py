@@ -43,6 +43,7 @@ C_ABI_SYMBOLS = (
     "fv_mae_loss_ok", "fv_mae_loss_fwd", "fv_mae_loss_bwd",
     "fv_mae_mask_plan", "fv_tokens_gather", "fv_mae_decoder_tokens_fwd", "fv_mae_decoder_tokens_bwd",
     "fv_resample_u8_ok", "fv_resample_workspace_ints", "fv_resample_coeffs", "fv_resample_u8",
+    "fv_randaug_ok", "fv_randaug_workspace_bytes", "fv_randaug_stats", "fv_randaug_apply",
 )
 
 
@@ -92,6 +93,7 @@ def lib():
         cdll.fv_mixer_scan_fwd_seg_floats.restype = ctypes.c_size_t
         cdll.fv_mixer_scan_bwd_seg_floats.restype = ctypes.c_size_t
         cdll.fv_resample_workspace_ints.restype = ctypes.c_longlong
+        cdll.fv_randaug_workspace_bytes.restype = ctypes.c_longlong
         _lib = _DeviceGuarded(cdll)
     return _lib
 

@@ -14,8 +14,8 @@ into the step's static uint8 input buffer, which ``fastvim_amd.pixels`` normalis
     step.step()                                            # or model(x_u8, mask_ratio=0.75) for MAE
 
 ``RandomResizedCrop`` is timm's draw (Python's ``random``, torchvision's flip on torch's CPU generator) without the pixels;
-``ResizeCenterCrop`` is the validation plan.  The supervised / fine-tune TRAINING loaders run RandAugment on the cropped PIL
-image and stay on the host.
+``ResizeCenterCrop`` is the validation plan.  The supervised / fine-tune TRAINING loaders run RandAugment on the crop: they
+resample into a temporary buffer and ``fastvim_amd.randaug.RandAugment.apply`` augments it on the device into ``x_u8``.
 
 The plan (one row of ``PLAN_INTS`` int32 per sample) and the pool live in device memory and are read when the launches
 RUN: captured in a graph (``slots=1``: one device pool, one address) they resample what the last ``commit()`` put there.

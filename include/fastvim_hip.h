@@ -80,7 +80,9 @@ const char* fv_last_error(void);
  *      d_model 192 with its weight streamed in MFMA fragment order); fv_gemm_bf16 is unchanged.
  *      Later, still 3: fv_resample_u8_ok, fv_resample_workspace_ints, fv_resample_coeffs and fv_resample_u8 were ADDED
  *      (bicubic resize, crop window and flip of uint8 images on the device, bit-exact to PIL); no existing entry point
- *      changed. */
+ *      changed.
+ *      Later, still 3: fv_randaug_ok, fv_randaug_workspace_bytes, fv_randaug_stats and fv_randaug_apply were ADDED
+ *      (RandAugment of planar uint8 batches on the device, bit-exact to PIL); no existing entry point changed. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -1096,6 +1098,64 @@ long long fv_resample_workspace_ints(int batch, int s_h, int s_w);
 int fv_resample_coeffs(const int* plan, long long pool_bytes, int* ws, int batch, int s_h, int s_w, fv_stream_t stream);
 int fv_resample_u8(const void* pool, long long pool_bytes, const int* plan, const int* ws, void* out, int batch, int s_h,
                    int s_w, fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Device-side RandAugment of a planar uint8 batch: one layer of timm's `RandAugment` (rand_augment_transform:
+ * imagenet_classification/datasets_supervised.py:193-207) per pair of launches, bit for bit what PIL computes for the op
+ * and argument the HOST drew (fastvim_amd/randaug.py).  Built without fast-math and with contraction off.
+ *
+ *   in, out  (batch, 3, s_h, s_w) uint8, planar, contiguous, distinct; any alignment.  `in` is only read.
+ *   plan     (batch, num_layers, FV_RANDAUG_PLAN_INTS) int32 in DEVICE memory, 8-byte aligned, read when the kernels
+ *            RUN (a replayed graph takes the plan of that moment).  The record of (sample, layer):
+ *              [0]       kind, FV_RA_* below; a value outside them is FV_RA_COPY
+ *              [1] [2]   arg0, arg1: SOLARIZE threshold | POSTERIZE bits kept | SOLARIZE_ADD addend, threshold
+ *              [3]       the float32 bits of the blend factor (COLOR, CONTRAST, BRIGHTNESS, SHARPNESS)
+ *              [4]       fill colour of AFFINE, R | G << 8 | B << 16
+ *              [5]       unused, 0
+ *              [6..17]   the six AFFINE coefficients (PIL's output-to-input map) as doubles, low word first
+ *   ws       fv_randaug_workspace_bytes(batch) bytes: per sample a (3, 256) uint8 table.  fv_randaug_stats writes it
+ *            for AUTOCONTRAST and EQUALIZE (the lookup table of each channel) and CONTRAST (byte 0: the mean grey
+ *            value); fv_randaug_apply of the SAME layer reads it.
+ *
+ * fv_randaug_stats: one launch over (channel, sample), 256 threads.  Workgroups of samples whose op needs no statistic
+ *   return at once.  Histograms are LDS integer atomics (order-independent); no global and no floating-point atomics.
+ *     AUTOCONTRAST (ImageOps.autocontrast, cutoff 0): lo / hi the first / last non-empty bin; identity if hi <= lo, else
+ *       fp64 scale = 255.0 / (hi - lo), offset = -lo * scale, lut[i] = clamp(trunc(i * scale + offset), 0, 255).
+ *     EQUALIZE (ImageOps.equalize): integers; identity with at most one non-empty bin or step = (sum - last non-empty
+ *       bin) / 255 == 0; else n = step / 2; lut[i] = min(n / step, 255); n += h[i].
+ *     CONTRAST: int(sum of grey / (s_h * s_w) + 0.5) in fp64, grey = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16.
+ * fv_randaug_apply: one launch over (tile of FV_RANDAUG_ROWS rows, sample), 256 threads; the kind is uniform in a
+ *   workgroup.  COPY copies.  The table ops (AUTOCONTRAST, EQUALIZE from ws; INVERT, SOLARIZE, POSTERIZE, SOLARIZE_ADD,
+ *   BRIGHTNESS and CONTRAST built in LDS from the record) are one lookup per byte.  COLOR and SHARPNESS are
+ *   Image.blend(degenerate, image, factor) in float32: degenerate + factor * (image - degenerate), one multiply and one
+ *   add, truncated for factors in [0, 1] and clipped otherwise; SHARPNESS's degenerate is ImageFilter.SMOOTH (borders
+ *   copied, float32 weights k / 13, accumulator from 0.5, rows y + 1, y, y - 1).  AFFINE is Image.transform(size, AFFINE,
+ *   m, BICUBIC, fillcolor) in fp64 (Geometry.c: bicubic_filter32RGB).  No atomics; the same inputs give the same bits.
+ * fv_randaug_ok: host code, the range both serve -- batch in [1, 4096], s_h and s_w in [8, 1024], num_layers in
+ *   [1, FV_RANDAUG_MAX_LAYERS].  `layer` is in [0, num_layers).
+ * ---------------------------------------------------------------------- */
+#define FV_RANDAUG_PLAN_INTS 18
+#define FV_RANDAUG_MAX_LAYERS 4
+#define FV_RANDAUG_WS_BYTES 768
+#define FV_RANDAUG_ROWS 8
+#define FV_RA_COPY 0
+#define FV_RA_AUTOCONTRAST 1
+#define FV_RA_EQUALIZE 2
+#define FV_RA_INVERT 3
+#define FV_RA_SOLARIZE 4
+#define FV_RA_POSTERIZE 5
+#define FV_RA_SOLARIZE_ADD 6
+#define FV_RA_COLOR 7
+#define FV_RA_CONTRAST 8
+#define FV_RA_BRIGHTNESS 9
+#define FV_RA_SHARPNESS 10
+#define FV_RA_AFFINE 11
+int fv_randaug_ok(int batch, int s_h, int s_w, int num_layers);
+long long fv_randaug_workspace_bytes(int batch);
+int fv_randaug_stats(const void* in, const int* plan, void* ws, int batch, int s_h, int s_w, int num_layers, int layer,
+                     fv_stream_t stream);
+int fv_randaug_apply(const void* in, void* out, const int* plan, const void* ws, int batch, int s_h, int s_w,
+                     int num_layers, int layer, fv_stream_t stream);
 
 #ifdef __cplusplus
 }
