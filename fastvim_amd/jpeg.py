@@ -1,0 +1,278 @@
+"""JPEG files straight into the uint8 loaders: the decode of the reference's ``datasets.ImageFolder`` --
+``Image.open(path).convert("RGB")``, libjpeg-turbo -- split the way GPU loaders split it.  ENTROPY DECODING STAYS ON THE
+HOST: marker parsing and Huffman decoding are serial and branchy (csrc/jpeg_host.cpp, plain C++).  Everything per pixel
+runs on the device (csrc/jpeg.hip): dequantisation, the 8 x 8 inverse DCT, fancy chroma upsampling and YCbCr -> RGB, byte
+for byte what libjpeg-turbo computes, written into the pixel pool ``fv_resample_u8`` already reads -- the resample
+launches run unchanged on it::
+
+    stage = JpegImageStage(B, 224, capacity_bytes=B << 20, coef_capacity_bytes=B << 20)
+    for k, raw in enumerate(files):                        # bytes of a .jpg
+        info = jpeg.probe(raw)
+        i, j, h, w, f = rrc.draw(info.height, info.width); stage.put_jpeg(k, raw, crop=(i, j, h, w), flip=f)
+    stage.commit(); stage.resample(out=x_u8)
+
+Only the MCUs the crop needs are kept (``mcu_window``), and Huffman decoding stops after the last of them.  The staged
+form is dense int16 coefficients, about 3 bytes per window pixel at 4:2:0 -- the order of the RGB crop it replaces.
+
+Served: baseline (SOF0) 8-bit Huffman files with one interleaved scan; grayscale, or YCbCr at 4:4:4, 4:2:2 (2x1) or 4:2:0
+(2x2).  A file outside that (progressive, arithmetic, 12-bit, CMYK, RGB-coded, other sampling, several scans, 16-bit
+tables), and a file the entropy decoder returns an error for, is decoded by PIL on the host and staged as ``put`` stages
+it -- identical by construction; ``last_jpeg_fallbacks`` counts them."""
+import ctypes
+import io
+import threading
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .resample import ImageStage, _pair, resample_ok
+
+REC_INTS = 224            # FV_JPEG_REC_INTS
+INFO_INTS = 8             # FV_JPEG_INFO_INTS
+S444, S422, S420, GRAY = 0, 1, 2, 3      # FV_JPEG_444 ..: PIL's ``subsampling`` numbers, and 3 for one component
+REASONS = ("served", "progressive", "arithmetic coding", "not 8-bit precision", "not 1 or 3 components",
+           "not YCbCr (Adobe transform 0 or RGB component ids)", "sampling factors", "several scans",
+           "16-bit quantisation tables", "malformed or not a JPEG", "frame type other than SOF0")
+ERRORS = {-10: "unserved", -11: "data ends early", -12: "bad Huffman code", -13: "run past 63", -14: "wrong restart marker",
+          -15: "coefficient capacity", -16: "window outside the image"}
+_MCU = ((1, 1), (2, 1), (2, 2), (1, 1))  # (h_max, v_max) of a sampling class
+
+
+class JpegInfo(NamedTuple):
+    height: int
+    width: int
+    subsampling: int      # 0: 4:4:4, 1: 4:2:2, 2: 4:2:0 (PIL's numbers), 3: grayscale, -1: unserved
+    served: bool
+    reason: str           # "served", or why not (REASONS)
+
+
+def _as_bytes(data):
+    return data if isinstance(data, bytes) else bytes(data)
+
+
+def _probe(data):
+    info = (ctypes.c_int * INFO_INTS)()
+    rc = L.host_lib().fv_jpeg_probe(ctypes.c_char_p(data), ctypes.c_longlong(len(data)), info)
+    if rc != 0:
+        raise RuntimeError(f"fv_jpeg_probe: code {rc}")
+    return list(info)
+
+
+def probe(data):
+    """What the header says, and whether the device path serves the file.  Host code of the library: no GPU needed."""
+    h, w, _, cls, ok, reason = _probe(_as_bytes(data))[:6]
+    return JpegInfo(h, w, cls, bool(ok), REASONS[reason])
+
+
+def mcu_window(height, width, subsampling, crop=None):
+    """The rectangle of MCUs ``(x0, y0, w, h)`` the crop ``(top, left, h, w)`` needs: the crop widened by 2 luma pixels on
+    every side where chroma is subsampled -- the fancy upsampler's true neighbour samples at an interior border --
+    clamped to the image, then widened to whole MCUs."""
+    hmax, vmax = _MCU[subsampling]
+    t, l, h, w = (0, 0, height, width) if crop is None else crop
+    px, py = 2 * (hmax > 1), 2 * (vmax > 1)
+    x0, x1 = max(l - px, 0), min(l + w + px, width)
+    y0, y1 = max(t - py, 0), min(t + h + py, height)
+    mw, mh = 8 * hmax, 8 * vmax
+    return x0 // mw, y0 // mh, -(-x1 // mw) - x0 // mw, -(-y1 // mh) - y0 // mh
+
+
+def window_elements(subsampling, window):
+    """int16 coefficients of a window: 64 per block, h_i * v_i blocks per MCU and component."""
+    hmax, vmax = _MCU[subsampling]
+    return window[2] * window[3] * 64 * (1 if subsampling == GRAY else hmax * vmax + 2)
+
+
+def entropy_decode(data, window=None):
+    """The host decoder on its own (no GPU): ``(record, coefficients)`` -- the int32 record of ``FV_JPEG_REC_INTS`` words
+    and the int16 coefficients of ``window`` (default: the whole image), as include/fastvim_hip.h lays them out.  Raises
+    ``ValueError`` with the decoder's reason."""
+    data = _as_bytes(data)
+    h, w, _, cls, ok, reason, mx, my = _probe(data)
+    if not ok:
+        raise ValueError(f"fv_jpeg_entropy_decode: unserved file ({REASONS[reason]})")
+    win = (0, 0, mx, my) if window is None else tuple(int(v) for v in window)
+    coef = np.zeros(max(window_elements(cls, win), 0), np.int16)
+    rec = np.zeros(REC_INTS, np.int32)
+    rc = L.host_lib().fv_jpeg_entropy_decode(ctypes.c_char_p(data), ctypes.c_longlong(len(data)), (ctypes.c_int * 4)(*win),
+                                             ctypes.c_void_p(coef.ctypes.data), ctypes.c_longlong(coef.size),
+                                             ctypes.c_void_p(rec.ctypes.data))
+    if rc != 0:
+        raise ValueError(f"fv_jpeg_entropy_decode: {ERRORS.get(rc, 'error')} (code {rc})")
+    return rec, coef
+
+
+def _pil_decode(data):
+    from PIL import Image
+    return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+
+
+class JpegImageStage(ImageStage):
+    """An ``ImageStage`` whose samples may also be put as JPEG FILES.  Each ring slot gains a pinned and a device pool of
+    int16 coefficients (``coef_capacity_bytes``) and the table of sample records; the plane workspace between the two JPEG
+    launches is shared by the slots like the resampler's coefficient workspace (launches of one stream are ordered).
+
+    ``put`` and ``put_jpeg`` may be mixed within a batch; a sample put as a decoded array has a zero-length JPEG job.
+    ``commit()`` also copies the used part of the coefficient pool and the table; ``resample(out)`` runs ``fv_jpeg_idct``
+    and ``fv_jpeg_rgb`` (``decode()``) in front of the two resample launches.  Their grids depend on the capacities only,
+    so with ``slots=1`` a captured ``resample`` replays correctly after a ``commit()`` of any other batch."""
+
+    def __init__(self, batch, out_size, capacity_bytes, coef_capacity_bytes, slots=2, device=None):
+        super().__init__(batch, out_size, capacity_bytes, slots=slots, device=device)
+        self.coef_elems = (int(coef_capacity_bytes) + 127) // 128 * 64
+        n = int(L.lib().fv_jpeg_table_ints(L.i32(self.batch)))
+        assert n == self.batch * REC_INTS + 2 * (self.batch + 1)
+        for s in self._slots:
+            s.coef_pin = torch.zeros(self.coef_elems, dtype=torch.int16).pin_memory()
+            s.table_pin = torch.zeros(n, dtype=torch.int32).pin_memory()
+            s.table_np = s.table_pin.numpy()
+            s.records = s.table_np[:self.batch * REC_INTS].reshape(self.batch, REC_INTS)
+            s.coef = torch.zeros(self.coef_elems, dtype=torch.int16, device=self.device)
+            s.table = torch.zeros(n, dtype=torch.int32, device=self.device)
+            s.jused, s.jfallbacks = 0, 0
+        self._planes = torch.zeros(self.coef_elems, dtype=torch.uint8, device=self.device)
+        self._lock = threading.RLock()
+        self.last_jpeg_fallbacks = 0
+        self.staged_coef_bytes = 0             # coefficient bytes of the batch committed last
+        self.staged_pool_bytes = 0             # of ``staged_bytes`` (pool bytes in use), those the host filled and sent
+
+    def _filling(self):
+        fresh = not self._open
+        s = super()._filling()
+        if fresh:
+            s.records[:, 0] = 0                # no JPEG job anywhere
+            s.jused, s.jfallbacks = 0, 0
+        return s
+
+    def put(self, i, array_hwc_u8, crop=None, out_full=None, window=(0, 0), flip=False):
+        with self._lock:
+            super().put(i, array_hwc_u8, crop=crop, out_full=out_full, window=window, flip=flip)
+
+    def _put_decoded(self, i, data, crop, out_full, window, flip):
+        try:
+            a = _pil_decode(data)
+        except ImportError:
+            raise ValueError(f"JpegImageStage.put_jpeg: sample {i} is outside the device path and PIL is not importable "
+                             "for the host fallback") from None
+        with self._lock:
+            self.put(i, a, crop=crop, out_full=out_full, window=window, flip=flip)
+            self._slots[self._fill].jfallbacks += 1
+
+    def put_jpeg(self, i, data, crop=None, out_full=None, window=(0, 0), flip=False):
+        """Stage sample ``i`` from the bytes of a JPEG file: the same meaning as ``put`` of the decoded image.  Reserves the
+        crop's region of the pixel pool, writes the ordinary plan row and entropy-decodes the MCUs the crop needs into the
+        pinned coefficient pool.  The decode is one ctypes call, and ctypes releases the GIL for its length: loader
+        threads that call ``put_jpeg`` for different samples decode in parallel (the reservations are under a lock)."""
+        i, data = int(i), _as_bytes(data)
+        H, W, _, cls, ok, _, _, _ = _probe(data)
+        if not ok:
+            return self._put_decoded(i, data, crop, out_full, window, flip)
+        t, l, h, w = (0, 0, H, W) if crop is None else (int(v) for v in crop)
+        if min(t, l) < 0 or h < 1 or w < 1 or t + h > H or l + w > W:
+            raise ValueError(f"ImageStage.put: crop {tuple(crop)} of sample {i} does not lie inside its {H}x{W} image")
+        o_h, o_w = (self.s_h, self.s_w) if out_full is None else _pair(out_full)
+        win_y, win_x = (int(v) for v in window)
+        if o_h < 1 or o_w < 1 or win_y < 0 or win_x < 0 or win_y + self.s_h > o_h or win_x + self.s_w > o_w:
+            raise ValueError(f"ImageStage.put: the {self.s_h}x{self.s_w} window at {(win_y, win_x)} of sample {i} does not lie "
+                             f"inside its {o_h}x{o_w} resize")
+        if not resample_ok(self.batch, self.s_h, self.s_w, h, w, o_h, o_w, win_y, win_x):
+            return self._put_decoded(i, data, crop, out_full, window, flip)      # ``put`` resizes it with PIL on the host
+        mcus = mcu_window(H, W, cls, (t, l, h, w))
+        n = window_elements(cls, mcus)
+        with self._lock:
+            s = self._filling()
+            if not 0 <= i < self.batch:
+                raise IndexError(f"ImageStage.put: sample {i} of a batch of {self.batch}")
+            if s.host.filled[i]:
+                raise ValueError(f"ImageStage.put: sample {i} was already put in this batch")
+            if s.jused + n > self.coef_elems:
+                raise ValueError(f"JpegImageStage.put_jpeg: sample {i} ({2 * n} coefficient bytes at offset {2 * s.jused}) "
+                                 f"overflows coef_capacity_bytes = {2 * self.coef_elems}")
+            off = s.host.reserve(i, h, w, o_h, o_w, win_y, win_x, flip)
+            base, s.jused = s.jused, s.jused + n
+        rec = s.records[i]
+        rc = L.host_lib().fv_jpeg_entropy_decode(ctypes.c_char_p(data), ctypes.c_longlong(len(data)), (ctypes.c_int * 4)(*mcus),
+                                                 ctypes.c_void_p(s.coef_pin.data_ptr() + 2 * base), ctypes.c_longlong(n),
+                                                 ctypes.c_void_p(rec.ctypes.data))
+        if rc != 0:
+            # a file the decoder gives up on: PIL's pixels into the region already reserved (PIL's own exception propagates
+            # for a file it rejects too)
+            rec[:] = 0
+            try:
+                a = _pil_decode(data)
+            except ImportError:
+                raise ValueError(f"JpegImageStage.put_jpeg: sample {i}: {ERRORS.get(rc, 'error')} (code {rc}), and PIL is not "
+                                 "importable for the host fallback") from None
+            np.copyto(s.host.pool[off:off + h * w * 3].reshape(h, w, 3), a[t:t + h, l:l + w])
+            with self._lock:
+                s.jfallbacks += 1
+            return
+        u = rec.view(np.uint32)
+        for c in range(1 if cls == GRAY else 3):                   # offsets relative to the sample -> to the pool
+            e = (int(u[9 + 2 * c]) | int(u[10 + 2 * c]) << 32) + base
+            u[9 + 2 * c], u[10 + 2 * c] = e & 0xffffffff, e >> 32
+        rec[19:23] = (t, l, h, w)
+        u[23], u[24] = off & 0xffffffff, off >> 32
+
+    def _copy_pool(self, s):
+        """Only the regions the HOST filled cross the link (samples put as arrays, fallbacks); a JPEG job's region is
+        written by ``fv_jpeg_rgb``.  Neighbouring host regions go as one copy -- what lies between them is overwritten by
+        the launches anyway."""
+        host = np.flatnonzero(s.records[:, 0] != 1)
+        spans = sorted((s.host.offset(i), int(s.host.plan[i, 2]) * int(s.host.plan[i, 3]) * 3) for i in host)
+        runs = []
+        for off, n in spans:
+            if runs and off - runs[-1][1] <= 4096:
+                runs[-1][1] = off + n
+            else:
+                runs.append([off, off + n])
+        for lo, hi in runs:
+            s.pool[lo:hi].copy_(s.pool_pin[lo:hi], non_blocking=True)
+        self.staged_pool_bytes = sum(n for _, n in spans)
+
+    def commit(self):
+        with self._lock:
+            s = self._filling()
+            s.host.check_complete()
+            r = s.records
+            job = r[:, 0] == 1
+            blocks = np.where(job, r[:, 17], 0).astype(np.int64)
+            quads = np.where(job, (r[:, 21].astype(np.int64) * r[:, 22] + 3) // 4, 0)
+            pre = np.zeros((2, self.batch + 1), np.int64)
+            np.cumsum(blocks, out=pre[0, 1:])
+            np.cumsum(quads, out=pre[1, 1:])
+            if pre.max() > 0x7fffffff:
+                raise ValueError("JpegImageStage.commit: more than 2^31 - 1 blocks or pixel quads in one batch")
+            s.table_np[self.batch * REC_INTS:] = pre.reshape(-1)
+            s.coef[:s.jused].copy_(s.coef_pin[:s.jused], non_blocking=True)
+            s.table.copy_(s.table_pin, non_blocking=True)
+            self.last_jpeg_fallbacks = s.jfallbacks
+            self.staged_coef_bytes = 2 * s.jused
+            super().commit()
+
+    def decode(self):
+        """The two JPEG launches on the slot committed last: coefficients -> sample planes (``fv_jpeg_idct``), planes ->
+        RGB crops in the pixel pool (``fv_jpeg_rgb``)."""
+        s = self._ready
+        if s is None:
+            raise RuntimeError("JpegImageStage.decode: nothing was committed")
+        lib, st = L.lib(), L.stream_of(s.pool)
+        ne, b = ctypes.c_longlong(self.coef_elems), L.i32(self.batch)
+        L.check(lib.fv_jpeg_idct(L.ptr(s.coef), ne, L.ptr(s.table), L.ptr(self._planes), ne, b, st), "fv_jpeg_idct")
+        L.check(lib.fv_jpeg_rgb(L.ptr(self._planes), ne, L.ptr(s.table), L.ptr(s.pool), ctypes.c_longlong(self.capacity), b, st),
+                "fv_jpeg_rgb")
+        self._record(s)
+
+    def region(self, i):
+        """The (h, w, 3) uint8 device view of sample ``i``'s source rectangle in the pool of the slot committed last."""
+        s = self._ready
+        h, w = (int(v) for v in s.host.plan[i, 2:4])
+        off = s.host.offset(i)
+        return s.pool[off:off + h * w * 3].view(h, w, 3)
+
+    def resample(self, out):
+        """``decode()``, then the two resample launches, into ``out`` (batch, 3, S_h, S_w) uint8."""
+        self.decode()
+        return super().resample(out)

@@ -191,11 +191,17 @@ class HostPlan:
             a = a[win_y:win_y + self.s_h, win_x:win_x + self.s_w]
             h, w, o_h, o_w, win_y, win_x = self.s_h, self.s_w, self.s_h, self.s_w, 0, 0
             self.fallbacks += 1
+        off = self.reserve(i, h, w, o_h, o_w, win_y, win_x, flip)
+        np.copyto(self.pool[off:off + h * w * 3].reshape(h, w, 3), a)
+        return off
+
+    def reserve(self, i, h, w, o_h, o_w, win_y, win_x, flip):
+        """Take the next ``h * w * 3`` bytes of the pool for sample ``i`` and write its plan row; the caller fills the
+        region -- ``put`` from the decoded array, ``fastvim_amd.jpeg`` on the device."""
         off = (self.used + ALIGN - 1) // ALIGN * ALIGN
         nbytes = h * w * 3
         if off + nbytes > self.capacity:
             raise ValueError(f"ImageStage.put: sample {i} ({nbytes} bytes at offset {off}) overflows capacity_bytes = {self.capacity}")
-        np.copyto(self.pool[off:off + nbytes].reshape(h, w, 3), a)
         self.plan[i] = (0, 0, h, w, o_h, o_w, win_y, win_x, int(bool(flip)), 0, 0, 0)
         self.plan.view(np.uint32)[i, :2] = (off & 0xffffffff, off >> 32)      # the byte offset as 64 bits, low word first
         self.used = off + nbytes
@@ -272,8 +278,7 @@ class ImageStage:
     def commit(self):
         s = self._filling()
         s.host.check_complete()
-        used = (s.host.used + ALIGN - 1) // ALIGN * ALIGN
-        s.pool[:used].copy_(s.pool_pin[:used], non_blocking=True)
+        self._copy_pool(s)
         s.plan.copy_(s.plan_pin, non_blocking=True)
         self._record(s)
         self.last_fallbacks = s.host.fallbacks
@@ -281,6 +286,11 @@ class ImageStage:
         self._ready = s
         self._open = False
         self._fill = (self._fill + 1) % len(self._slots)
+
+    def _copy_pool(self, s):
+        """The pool bytes the host filled, to the device (``JpegImageStage`` leaves out what the device fills itself)."""
+        used = (s.host.used + ALIGN - 1) // ALIGN * ALIGN
+        s.pool[:used].copy_(s.pool_pin[:used], non_blocking=True)
 
     def _record(self, s):
         if torch.cuda.is_current_stream_capturing():

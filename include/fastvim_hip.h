@@ -82,7 +82,10 @@ const char* fv_last_error(void);
  *      (bicubic resize, crop window and flip of uint8 images on the device, bit-exact to PIL); no existing entry point
  *      changed.
  *      Later, still 3: fv_randaug_ok, fv_randaug_workspace_bytes, fv_randaug_stats and fv_randaug_apply were ADDED
- *      (RandAugment of planar uint8 batches on the device, bit-exact to PIL); no existing entry point changed. */
+ *      (RandAugment of planar uint8 batches on the device, bit-exact to PIL); no existing entry point changed.
+ *      Later, still 3: fv_jpeg_probe, fv_jpeg_entropy_decode, fv_jpeg_table_ints, fv_jpeg_idct and fv_jpeg_rgb were ADDED
+ *      (JPEG decode split between a host entropy decoder and two device launches, byte-exact to PIL); no existing entry
+ *      point changed. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -1156,6 +1159,89 @@ int fv_randaug_stats(const void* in, const int* plan, void* ws, int batch, int s
                      fv_stream_t stream);
 int fv_randaug_apply(const void* in, void* out, const int* plan, const void* ws, int batch, int s_h, int s_w,
                      int num_layers, int layer, fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Device-side JPEG decode after host entropy decoding, byte for byte what libjpeg-turbo (PIL's
+ * `Image.open(...).convert("RGB")`, the reference's datasets.ImageFolder loader) gives.  The serial part stays on the
+ * HOST: marker parsing and Huffman decoding (csrc/jpeg_host.cpp, plain C++, no HIP; these two entry points touch no GPU
+ * and keep no state -- any number of threads may call them; they report through their return value, not fv_last_error).
+ * Everything per pixel runs on the device (csrc/jpeg.hip): dequantisation, the 8 x 8 inverse DCT, fancy chroma
+ * upsampling and YCbCr -> RGB, written straight into the pixel pool fv_resample_u8 reads.
+ *
+ * Served (fv_jpeg_probe): SOF0, 8-bit precision, one interleaved scan of all components, Huffman coding, 8-bit
+ * quantisation tables; one component, sampled 1x1 (FV_JPEG_GRAY), or three read as YCbCr with chroma sampled 1x1 and luma
+ * 1x1 (FV_JPEG_444), 2x1 (FV_JPEG_422) or 2x2 (FV_JPEG_420).  Everything else is unserved with a FV_JPEG_R_* reason.
+ *
+ * fv_jpeg_probe(data, nbytes, info): info[FV_JPEG_INFO_INTS] = height, width, components, sampling class (-1 when
+ *   unserved), served (0 / 1), reason, MCUs per row, MCU rows.  Returns FV_OK (also for an unserved file: the reason is the
+ *   answer) or FV_ERR_INVALID for a null pointer.
+ * fv_jpeg_entropy_decode(data, nbytes, window, coef_out, coef_capacity, record): window[4] = x0, y0, w, h is a rectangle
+ *   of MCUs inside the image.  MCUs are decoded in file order up to the LAST one the window needs; the quantised
+ *   coefficients of the blocks inside the window are written as int16 in NATURAL order, component after component, each a
+ *   dense (h * v_i block rows, w * h_i block columns, 64) array starting at coef_out; `coef_capacity` counts int16
+ *   ELEMENTS.  Byte stuffing, fill bytes, restart intervals (predictors reset, marker sequence checked), EOB and ZRL are
+ *   handled.  Returns FV_OK or a FV_JPEG_E_* code; on an error the record and the coefficients are unspecified and must
+ *   not be used (there is no partial result).  Reads only [data, data + nbytes), writes only coef_out[0 : coef_capacity]
+ *   and record[0 : FV_JPEG_REC_INTS].  The record, int32:
+ *     [0]        1: a JPEG job (0: none -- a sample staged as a decoded array)
+ *     [1] [2]    image height, width          [3] components          [4] sampling class
+ *     [5..8]     the window: x0, y0, w, h in MCUs
+ *     [9..14]    per component the offset of its coefficients in ELEMENTS, low and high 32 bits -- relative to coef_out as
+ *                the decoder writes them; the caller adds the offset of coef_out in the pool.  The component's sample
+ *                plane lies at the same offset, in bytes, of the plane workspace.
+ *     [15] [16]  elements written, low and high    [17] blocks written    [18] MCUs decoded
+ *     [19..22]   CALLER: the crop top, left, height, width in image pixels (inside the window's interior: see jpeg.py)
+ *     [23] [24]  CALLER: byte offset of the crop's h x w x 3 region in the pixel pool, low and high
+ *     [25..31]   0
+ *     [32..223]  the quantisation table of each component, 64 words, natural order
+ *
+ * The two launches read a TABLE in device memory when they RUN (a replayed graph takes the table, the coefficients and
+ * the pools of that moment): `batch` records, then batch + 1 int32 prefix sums of the records' block counts, then
+ * batch + 1 prefix sums of their pixel quads, ceil(crop h * crop w / 4) -- fv_jpeg_table_ints(batch) words.  Their grids
+ * depend on the capacities only (each workgroup takes a contiguous share of the work the table states).  Every coefficient and plane access is checked against `coef_elems`
+ * / `plane_bytes` and every pixel write against `pool_bytes`; a record that does not fit is skipped.  No atomics.
+ * fv_jpeg_idct: every block: coefficient x table entry in 32-bit integers, jidctint's "islow" inverse DCT (CONST_BITS 13,
+ *   PASS1_BITS 2; columns first, (v + 1024) >> 11; then rows, (v + 131072) >> 18), + 128, clamped to 0..255, into the
+ *   component's plane (window-local pitch: block columns * 8).  8 lanes per block.  `planes` holds plane_bytes >=
+ *   coef_elems bytes, 8-byte aligned; coef 16-byte aligned.
+ * fv_jpeg_rgb: every pixel of every crop: luma, chroma upsampled as jdsample's fancy h2v1 / h2v2 upsamplers do over the
+ *   TRUE plane sizes ceil(W / h_max) x ceil(H / v_max), jdcolor's 16-bit fixed-point conversion, three bytes into the
+ *   pool (HWC, pitch 3 w).  A crop's region must start 4-byte aligned in a 4-byte aligned pool.
+ * For coefficient values no encoder writes the pixel values are unspecified (32-bit wrap-around, not libjpeg's 64-bit
+ * intermediates and masked range table); memory safety holds regardless.
+ * ---------------------------------------------------------------------- */
+#define FV_JPEG_INFO_INTS 8
+#define FV_JPEG_REC_INTS 224
+#define FV_JPEG_444 0
+#define FV_JPEG_422 1
+#define FV_JPEG_420 2
+#define FV_JPEG_GRAY 3
+#define FV_JPEG_R_OK 0
+#define FV_JPEG_R_PROGRESSIVE 1
+#define FV_JPEG_R_ARITHMETIC 2
+#define FV_JPEG_R_PRECISION 3
+#define FV_JPEG_R_COMPONENTS 4
+#define FV_JPEG_R_COLOUR 5
+#define FV_JPEG_R_SAMPLING 6
+#define FV_JPEG_R_SCANS 7
+#define FV_JPEG_R_TABLES16 8
+#define FV_JPEG_R_MALFORMED 9
+#define FV_JPEG_R_FRAME 10
+#define FV_JPEG_E_UNSERVED (-10)
+#define FV_JPEG_E_TRUNCATED (-11)
+#define FV_JPEG_E_CODE (-12)
+#define FV_JPEG_E_RUN (-13)
+#define FV_JPEG_E_RESTART (-14)
+#define FV_JPEG_E_CAPACITY (-15)
+#define FV_JPEG_E_WINDOW (-16)
+int fv_jpeg_probe(const void* data, long long nbytes, int* info);
+int fv_jpeg_entropy_decode(const void* data, long long nbytes, const int* window, int16_t* coef_out,
+                           long long coef_capacity, int* record);
+long long fv_jpeg_table_ints(int batch);
+int fv_jpeg_idct(const void* coef, long long coef_elems, const int* table, void* planes, long long plane_bytes, int batch,
+                 fv_stream_t stream);
+int fv_jpeg_rgb(const void* planes, long long plane_bytes, const int* table, void* pool, long long pool_bytes, int batch,
+                fv_stream_t stream);
 
 #ifdef __cplusplus
 }
