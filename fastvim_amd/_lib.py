@@ -45,6 +45,7 @@ C_ABI_SYMBOLS = (
     "fv_resample_u8_ok", "fv_resample_workspace_ints", "fv_resample_coeffs", "fv_resample_u8",
     "fv_randaug_ok", "fv_randaug_workspace_bytes", "fv_randaug_stats", "fv_randaug_apply",
     "fv_jpeg_probe", "fv_jpeg_entropy_decode", "fv_jpeg_table_ints", "fv_jpeg_idct", "fv_jpeg_rgb",
+    "fv_mae_noise", "fv_mae_mask_plan_keyed",
 )
 
 

@@ -6,6 +6,9 @@
 //                              L LDS broadcast reads per thread); the K lowest ranks are kept; a kept token's position among
 //                              the kept ones is a ballot prefix count in token order, its position in the TRANSPOSED grid's
 //                              scan order (the odd layers) the same count over the flags stored transposed.
+//   mae_mask_plan_keyed_kernel the same plan of the noise of a KEY BLOCK (mask_noise.h: Philox4x32-10 of (key, step, sample, token)),
+//                              generated into the LDS keys by the first L / 4 threads: the noise is never in memory.
+//   mae_noise_kernel           that noise written out, (B, L) fp32: the eager form, the tests' and the fallback paths'.
 //   tokens_gather_kernel       out[b, t, :] = in[b, index[b, t], :], a zero row where the index is outside [0, Lin).  A thread
 //                              moves 4 (mixed / fp32) or 8 (bf16 -> bf16) channels: 16-byte accesses.  Same type in and out:
 //                              a bit copy.  With unique indices the adjoint of a gather is the gather by the inverse index
@@ -18,6 +21,7 @@
 //                              (sixteen strided walks, then a fixed tree).  No atomics: the same inputs give the same bits.
 // Floating-point reassociation and contraction are switched off for the whole file: every sum has ONE order, the one written.
 #include "common.h"
+#include "mask_noise.h"
 #include "rowwalk.h"
 
 #pragma clang fp reassociate(off) contract(off)
@@ -63,16 +67,11 @@ __device__ __forceinline__ int block_prefix_count(bool flag, int* totals) {
   return base + before;
 }
 
-__global__ __launch_bounds__(1024) void mae_mask_plan_kernel(const float* __restrict__ noise, PlanOut o, int B, int H, int W,
-                                                             int K) {
-  __shared__ uint32_t s_key[MP_MAX_L];
-  __shared__ int s_pos[MP_MAX_L];             // kept position of token i, -1 = removed
-  __shared__ unsigned char s_keptT[MP_MAX_L]; // kept flag at the token's place in the transposed grid
-  __shared__ int s_tot[16];
+// The plan of one sample from its L keys in LDS (both plan kernels; the caller has synchronised behind the writes of s_key).
+__device__ __forceinline__ void plan_from_keys(const uint32_t* s_key, int* s_pos, unsigned char* s_keptT, int* s_tot,
+                                               const PlanOut& o, int B, int H, int W, int K) {
   const int L = H * W, b = blockIdx.x, i = threadIdx.x;       // blockDim.x >= L
   const bool live = i < L;
-  if (live) s_key[i] = order_key(__float_as_uint(noise[(size_t)b * L + i]));
-  __syncthreads();
   int rank = 0;
   if (live) {
     const uint32_t ki = s_key[i];
@@ -116,6 +115,53 @@ __global__ __launch_bounds__(1024) void mae_mask_plan_kernel(const float* __rest
     o.row_index_odd[bk + q] = rt;
     o.row_index_odd[(size_t)B * K + bk + (K - 1 - q)] = (W - 1) - rt;
   }
+}
+
+__global__ __launch_bounds__(1024) void mae_mask_plan_kernel(const float* __restrict__ noise, PlanOut o, int B, int H, int W,
+                                                             int K) {
+  __shared__ uint32_t s_key[MP_MAX_L];
+  __shared__ int s_pos[MP_MAX_L];             // kept position of token i, -1 = removed
+  __shared__ unsigned char s_keptT[MP_MAX_L]; // kept flag at the token's place in the transposed grid
+  __shared__ int s_tot[16];
+  const int L = H * W, b = blockIdx.x, i = threadIdx.x;       // blockDim.x >= L
+  if (i < L) s_key[i] = order_key(__float_as_uint(noise[(size_t)b * L + i]));
+  __syncthreads();
+  plan_from_keys(s_key, s_pos, s_keptT, s_tot, o, B, H, W, K);
+}
+
+// The same plan with the noise made here (mask_noise.h) instead of loaded: thread t < ceil(L / 4) runs the Philox rounds of
+// token group t and puts its (up to) four keys into LDS; no (B, L) tensor exists.
+__global__ __launch_bounds__(1024) void mae_mask_plan_keyed_kernel(const int32_t* __restrict__ block, PlanOut o, int B, int H,
+                                                                   int W, int K) {
+  __shared__ uint32_t s_key[MP_MAX_L];
+  __shared__ int s_pos[MP_MAX_L];
+  __shared__ unsigned char s_keptT[MP_MAX_L];
+  __shared__ int s_tot[16];
+  const int L = H * W, b = blockIdx.x, t = threadIdx.x;       // blockDim.x >= L >= ceil(L / 4)
+  if (4 * t < L) {
+    float u[4];
+    fv_mask::noise4(fv_mask::load_key(block), b, t, u);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (4 * t + k < L) s_key[4 * t + k] = order_key(__float_as_uint(u[k]));
+  }
+  __syncthreads();
+  plan_from_keys(s_key, s_pos, s_keptT, s_tot, o, B, H, W, K);
+}
+
+// noise (B, L) fp32 of the key block: one thread per (sample, group of four tokens)
+__global__ __launch_bounds__(256) void mae_noise_kernel(const int32_t* __restrict__ block, float* __restrict__ noise, long units,
+                                                        int G, int L) {
+  const long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= units) return;
+  const long b = v / G;
+  const int g = (int)(v - b * G);
+  float u[4];
+  fv_mask::noise4(fv_mask::load_key(block), (int)b, g, u);
+  float* dst = noise + (size_t)b * L + 4 * g;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (4 * g + k < L) dst[k] = u[k];
 }
 
 // ---- row gather.  One thread per (output row, VEC channels).
@@ -240,26 +286,60 @@ bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
 }  // namespace
 
+namespace {
+// the checks both plan entry points share; `src` is the noise tensor or the key block (4-byte elements either way)
+int plan_check(const char* who, const void* src, const PlanOut& o, int batch, int grid_h, int grid_w, int len_keep) {
+  FV_CHECK(src && o.ids_keep && o.ids_restore && o.mask && o.keep_index && o.restore_index && o.row_index_even && o.ids_keep_odd &&
+               o.order && o.inverse && o.order_index && o.inverse_index && o.row_index_odd, "%s: null pointer", who);
+  FV_CHECK(batch > 0 && grid_h > 0 && grid_w > 0 && (long)grid_h * grid_w <= MP_MAX_L,
+           "%s: batch %d, grid %d x %d: needs a non-empty grid of at most %d tokens", who, batch, grid_h, grid_w, MP_MAX_L);
+  FV_CHECK(len_keep >= 1 && len_keep <= grid_h * grid_w, "%s: len_keep %d outside [1, %d]", who, len_keep, grid_h * grid_w);
+  FV_CHECK(aligned_to(src, 4) && aligned_to(o.mask, 4) && aligned_to(o.keep_index, 4) && aligned_to(o.restore_index, 4) &&
+               aligned_to(o.row_index_even, 4) && aligned_to(o.order_index, 4) && aligned_to(o.inverse_index, 4) &&
+               aligned_to(o.row_index_odd, 4) && aligned_to(o.ids_keep, 8) && aligned_to(o.ids_restore, 8) &&
+               aligned_to(o.ids_keep_odd, 8) && aligned_to(o.order, 8) && aligned_to(o.inverse, 8),
+           "%s: a buffer is not aligned to its element size", who);
+  return FV_OK;
+}
+int plan_threads(int L) { return ((L + FV_WAVE - 1) / FV_WAVE) * FV_WAVE; }        // one thread per token, whole waves
+}  // namespace
+
 extern "C" int fv_mae_mask_plan(const float* noise, long long* ids_keep, long long* ids_restore, float* mask, int* keep_index,
                                 int* restore_index, int* row_index_even, long long* ids_keep_odd, long long* order,
                                 long long* inverse, int* order_index, int* inverse_index, int* row_index_odd, int batch,
                                 int grid_h, int grid_w, int len_keep, fv_stream_t stream) {
-  FV_CHECK(noise && ids_keep && ids_restore && mask && keep_index && restore_index && row_index_even && ids_keep_odd && order &&
-               inverse && order_index && inverse_index && row_index_odd, "mae_mask_plan: null pointer");
-  FV_CHECK(batch > 0 && grid_h > 0 && grid_w > 0 && (long)grid_h * grid_w <= MP_MAX_L,
-           "mae_mask_plan: batch %d, grid %d x %d: needs a non-empty grid of at most %d tokens", batch, grid_h, grid_w, MP_MAX_L);
-  const int L = grid_h * grid_w;
-  FV_CHECK(len_keep >= 1 && len_keep <= L, "mae_mask_plan: len_keep %d outside [1, %d]", len_keep, L);
-  FV_CHECK(aligned_to(noise, 4) && aligned_to(mask, 4) && aligned_to(keep_index, 4) && aligned_to(restore_index, 4) &&
-               aligned_to(row_index_even, 4) && aligned_to(order_index, 4) && aligned_to(inverse_index, 4) &&
-               aligned_to(row_index_odd, 4) && aligned_to(ids_keep, 8) && aligned_to(ids_restore, 8) &&
-               aligned_to(ids_keep_odd, 8) && aligned_to(order, 8) && aligned_to(inverse, 8),
-           "mae_mask_plan: a buffer is not aligned to its element size");
   PlanOut o{ids_keep, ids_restore, mask, keep_index, restore_index, row_index_even, ids_keep_odd, order, inverse, order_index,
             inverse_index, row_index_odd};
-  const int threads = ((L + FV_WAVE - 1) / FV_WAVE) * FV_WAVE;        // one thread per token, whole waves
-  hipLaunchKernelGGL(mae_mask_plan_kernel, dim3(batch), dim3(threads), 0, (hipStream_t)stream, noise, o, batch, grid_h, grid_w,
-                     len_keep);
+  const int rc = plan_check("mae_mask_plan", noise, o, batch, grid_h, grid_w, len_keep);
+  if (rc != FV_OK) return rc;
+  hipLaunchKernelGGL(mae_mask_plan_kernel, dim3(batch), dim3(plan_threads(grid_h * grid_w)), 0, (hipStream_t)stream, noise, o,
+                     batch, grid_h, grid_w, len_keep);
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
+extern "C" int fv_mae_noise(const int32_t* block, float* noise, int batch, int len, fv_stream_t stream) {
+  FV_CHECK(block && noise, "mae_noise: null pointer");
+  FV_CHECK(batch > 0 && len > 0, "mae_noise: batch %d, len %d: empty", batch, len);
+  FV_CHECK(aligned_to(block, 4) && aligned_to(noise, 4), "mae_noise: a buffer is not aligned to its element size");
+  const int G = (len + 3) / 4;
+  const long units = (long)batch * G;
+  FV_CHECK(units <= 0x7fffffffL, "mae_noise: too many tokens");
+  hipLaunchKernelGGL(mae_noise_kernel, dim3(fv_cdiv(units, 256)), dim3(256), 0, (hipStream_t)stream, block, noise, units, G, len);
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
+extern "C" int fv_mae_mask_plan_keyed(const int32_t* block, long long* ids_keep, long long* ids_restore, float* mask,
+                                      int* keep_index, int* restore_index, int* row_index_even, long long* ids_keep_odd,
+                                      long long* order, long long* inverse, int* order_index, int* inverse_index,
+                                      int* row_index_odd, int batch, int grid_h, int grid_w, int len_keep, fv_stream_t stream) {
+  PlanOut o{ids_keep, ids_restore, mask, keep_index, restore_index, row_index_even, ids_keep_odd, order, inverse, order_index,
+            inverse_index, row_index_odd};
+  const int rc = plan_check("mae_mask_plan_keyed", block, o, batch, grid_h, grid_w, len_keep);
+  if (rc != FV_OK) return rc;
+  hipLaunchKernelGGL(mae_mask_plan_keyed_kernel, dim3(batch), dim3(plan_threads(grid_h * grid_w)), 0, (hipStream_t)stream, block,
+                     o, batch, grid_h, grid_w, len_keep);
   FV_LAUNCH_CHECK();
   return FV_OK;
 }

@@ -86,11 +86,16 @@ class MaskedAutoencoderViM(_FastVimMAE):
     def no_weight_decay(self):
         return {"pos_embed", "cls_token", "dist_token"}
 
-    def forward_encoder(self, x, mask_ratio, inference_params=None, noise=None):
+    # The class token sits in the middle of the kept tokens and the blocks take no plan: this model does not share the FastVim
+    # MAE's loops, so it does not offer the segment protocol of fastvim_amd.mae_step.MAEPretrainStep (which names the
+    # missing method in its TypeError).
+    _embed_masked = _run_layers = _tail = None
+
+    def forward_encoder(self, x, mask_ratio, inference_params=None, noise=None, sampler=None):
         """:583-631: patch embedding + position (the class slot of ``pos_embed`` goes to the class token), masking, the
         class token in the MIDDLE of the kept tokens, Vim blocks, final norm."""
         x = self.patch_embed(x, self.pos_embed[:, 1:, :])
-        x, mask, ids_restore, _ = self.random_masking(x, mask_ratio, noise)
+        x, mask, ids_restore, _ = self.random_masking(x, mask_ratio, noise, sampler)
         M = x.shape[1]
         cls_tokens = (self.cls_token + self.pos_embed[:, :1, :]).expand(x.shape[0], -1, -1).to(x.dtype)
         token_position = M // 2
@@ -101,10 +106,10 @@ class MaskedAutoencoderViM(_FastVimMAE):
             hidden_states, residual = layer(hidden_states, residual, inference_params=inference_params)
         return self._final_norm(self.norm_f, hidden_states, residual), mask, ids_restore
 
-    def _encode(self, x, mask_ratio, inference_params=None, noise=None):
-        # ``fused_tokens`` reaches the inherited ``random_masking`` only: the decoder assembly below, with its class token,
-        # keeps the torch chain, so no plan is handed on
-        return (*self.forward_encoder(x, mask_ratio, inference_params, noise=noise), None)
+    def _encode(self, x, mask_ratio, inference_params=None, noise=None, sampler=None):
+        # ``fused_tokens`` (and a ``sampler``'s keyed plan) reach the inherited ``random_masking`` only: the decoder assembly
+        # below, with its class token, keeps the torch chain, so no plan is handed on
+        return (*self.forward_encoder(x, mask_ratio, inference_params, noise=noise, sampler=sampler), None)
 
     def forward_decoder(self, x, ids_restore, inference_params=None):
         """:633-691: mask tokens appended and unshuffled WITHOUT the class token, which is re-attached at the END of the

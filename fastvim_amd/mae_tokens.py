@@ -11,13 +11,16 @@ sum over the removed rows, here in fp64 in a fixed order (deterministic), in eag
 
 Nothing here synchronises with the host; outputs are allocated by torch on the current stream: safe under graph capture.
 """
+import struct
 from typing import NamedTuple
 
 import torch
 
 from . import _lib as L
+from ._devblock import BlockWriter
 
-MAX_TOKENS = 1024                # FV_MAE_PLAN_MAX_TOKENS: 32 x 32, FastVim-H at 448 px
+_M64 = (1 << 64) - 1
+MAX_TOKENS = 1024               # FV_MAE_PLAN_MAX_TOKENS: 32 x 32, FastVim-H at 448 px
 MIN_KEEP = 3                     # the masked mixer's conv halo
 DECODER_ROWS_PER_BLOCK = 32      # FV_MAE_DECODER_ROWS_PER_BLOCK
 _DTYPES = (torch.float32, torch.bfloat16)
@@ -65,19 +68,122 @@ def mask_plan(noise, token_size, len_keep):
     H, W, K = int(token_size[0]), int(token_size[1]), int(len_keep)
     noise = noise.detach()
     N, Ln = noise.shape
-    dev = noise.device
-    i64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int64)
-    i32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int32)
-    plan = TokenPlan(ids_keep=i64(N, K), ids_restore=i64(N, Ln), mask=torch.empty(N, Ln, device=dev, dtype=torch.float32),
-                     keep_index=i32(N, K), restore_index=i32(N, Ln), row_index_even=i32(2, N, K), ids_keep_odd=i64(N, K),
-                     order=i64(N, K), inverse=i64(N, K), order_index=i32(N, K), inverse_index=i32(N, K),
-                     row_index_odd=i32(2, N, K), token_size=(H, W))
+    plan = _empty_plan(N, H, W, K, noise.device)
     rc = L.lib().fv_mae_mask_plan(L.ptr(noise), L.ptr(plan.ids_keep), L.ptr(plan.ids_restore), L.ptr(plan.mask),
                                   L.ptr(plan.keep_index), L.ptr(plan.restore_index), L.ptr(plan.row_index_even),
                                   L.ptr(plan.ids_keep_odd), L.ptr(plan.order), L.ptr(plan.inverse), L.ptr(plan.order_index),
                                   L.ptr(plan.inverse_index), L.ptr(plan.row_index_odd), L.i32(N), L.i32(H), L.i32(W), L.i32(K),
                                   L.stream_of(noise))
     L.check(rc, "mae_mask_plan")
+    return plan
+
+
+def plan_shape_ok(batch, token_size, len_keep):
+    """The part of the plan's predicate that is about sizes: ``batch`` >= 1, an (H, W) grid of at most 1024 tokens,
+    3 <= len_keep <= H W.  What ``mask_plan_keyed`` asks (it has no noise tensor to check).  Pure Python."""
+    H, W = int(token_size[0]), int(token_size[1])
+    if int(batch) <= 0 or H <= 0 or W <= 0 or H * W > MAX_TOKENS:
+        return False
+    return MIN_KEEP <= int(len_keep) <= H * W
+
+
+def _empty_plan(N, H, W, K, dev):
+    Ln = H * W
+    i64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int64)
+    i32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int32)
+    return TokenPlan(ids_keep=i64(N, K), ids_restore=i64(N, Ln), mask=torch.empty(N, Ln, device=dev, dtype=torch.float32),
+                     keep_index=i32(N, K), restore_index=i32(N, Ln), row_index_even=i32(2, N, K), ids_keep_odd=i64(N, K),
+                     order=i64(N, K), inverse=i64(N, K), order_index=i32(N, K), inverse_index=i32(N, K),
+                     row_index_odd=i32(2, N, K), token_size=(H, W))
+
+
+class MaskSampler:
+    """The MAE masking noise as a function of ``(seed, counter, sample, token)`` instead of a draw from torch's generator: the
+    same masks on any device, after a resume, and from the CPU (tests/mask_noise_ref.py restates it in numpy).
+
+    The noise of sample b, token l is ``float(w >> 8) * 2**-24`` with ``w`` word ``l & 3`` of Philox4x32-10 under key
+    ``(seed & 0xffffffff, seed >> 32)`` and counter ``(l >> 2, b, counter & 0xffffffff, counter >> 32)`` (csrc/mask_noise.h).
+    The four words ``(k0, k1, step_lo, step_hi)`` live in a KEY BLOCK in device memory that the kernels read when they RUN:
+    ``sample()`` advances the 64-bit counter (from 0: the first masks are those of counter 1) and rewrites the block from
+    pinned memory on the current stream, so a replayed graph masks with the counter of the last ``sample()`` -- the technique
+    of ``Mixup.sample()`` and ``RandomErasing.sample()``.  Data-parallel ranks pass DIFFERENT seeds (``seed=rank``).  torch's
+    generators are never touched."""
+
+    def __init__(self, seed=0):
+        self.seed, self.counter = int(seed) & _M64, 0
+        self._block = None
+        self._writer = None
+
+    # ------------------------------------------------------------------ host side
+    def words(self):
+        """``(k0, k1, step_lo, step_hi)``: the key block for the current ``(seed, counter)``, four 32-bit words."""
+        return (self.seed & 0xffffffff, self.seed >> 32, self.counter & 0xffffffff, self.counter >> 32)
+
+    def sample(self):
+        """Advance the counter -- new masks for the next step -- and write the block.  Returns ``last()``."""
+        self.counter = (self.counter + 1) & _M64
+        self._write()
+        return self.last()
+
+    def last(self):
+        """``(seed, counter)`` of the masks the next launch takes."""
+        return self.seed, self.counter
+
+    def set_counter(self, n):
+        self.counter = int(n) & _M64
+        self._write()
+
+    def state_dict(self):
+        return {"seed": self.seed, "counter": self.counter}
+
+    def load_state_dict(self, state):
+        self.seed, self.counter = int(state["seed"]) & _M64, int(state["counter"]) & _M64
+        self._write()
+
+    # ------------------------------------------------------------------ device side
+    def block(self, device=None):
+        """The device key block (int32[4]), created on first use and rewritten by every ``sample()`` from then on."""
+        if self._block is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+            if device.type != "cuda":
+                raise RuntimeError("fastvim_amd ops run on the GPU only (HIP kernels); the key block needs a GPU device")
+            self._block = torch.zeros(4, device=device, dtype=torch.int32)
+            self._writer = BlockWriter(4)
+            self._write()
+        elif device is not None and torch.device(device).type == "cuda" and torch.device(device).index not in (None, self._block.device.index):
+            raise RuntimeError(f"MaskSampler: the key block lives on {self._block.device}, the tensors on {device}")
+        return self._block
+
+    def _write(self):
+        if self._block is None:
+            return
+        # an asynchronous copy from pinned memory on the current stream, no host wait (fastvim_amd/_devblock.py)
+        self._writer.write(self._block, struct.pack("<4I", *self.words()))
+
+    def noise(self, B, Ln, device=None):
+        """The (B, L) fp32 noise of the current ``(seed, counter)``: one ``fv_mae_noise`` launch."""
+        blk = self.block(device)
+        out = torch.empty(int(B), int(Ln), device=blk.device, dtype=torch.float32)
+        rc = L.lib().fv_mae_noise(L.ptr(blk), L.ptr(out), L.i32(B), L.i32(Ln), L.stream_of(out))
+        L.check(rc, "mae_noise")
+        return out
+
+
+def mask_plan_keyed(sampler, batch, token_size, len_keep, device=None):
+    """``mask_plan(sampler.noise(batch, H W), token_size, len_keep)`` from ONE launch in which the noise never reaches
+    memory (``fv_mae_mask_plan_keyed``): every field bit for bit the same.  Raises where ``plan_shape_ok`` says no."""
+    if not plan_shape_ok(batch, token_size, len_keep):
+        raise RuntimeError(f"mask_plan_keyed: unsupported arguments (batch {batch}, token_size {tuple(token_size)}, "
+                           f"len_keep {len_keep}); see plan_shape_ok")
+    N, H, W, K = int(batch), int(token_size[0]), int(token_size[1]), int(len_keep)
+    blk = sampler.block(device)
+    plan = _empty_plan(N, H, W, K, blk.device)
+    rc = L.lib().fv_mae_mask_plan_keyed(L.ptr(blk), L.ptr(plan.ids_keep), L.ptr(plan.ids_restore), L.ptr(plan.mask),
+                                        L.ptr(plan.keep_index), L.ptr(plan.restore_index), L.ptr(plan.row_index_even),
+                                        L.ptr(plan.ids_keep_odd), L.ptr(plan.order), L.ptr(plan.inverse),
+                                        L.ptr(plan.order_index), L.ptr(plan.inverse_index), L.ptr(plan.row_index_odd),
+                                        L.i32(N), L.i32(H), L.i32(W), L.i32(K), L.stream_of(plan.mask))
+    L.check(rc, "mae_mask_plan_keyed")
     return plan
 
 

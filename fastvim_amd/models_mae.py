@@ -11,7 +11,9 @@ gather kernels (fastvim_amd/mae_tokens.py).
 One extension over the reference API: ``random_masking`` / ``forward`` / ``forward_encoder`` accept ``noise``
 (N, L) -- the per-token uniform scores whose argsort decides which tokens are kept -- so that a run can be
 reproduced across devices (torch's CPU and GPU generators differ); ``noise=None`` draws it exactly like the
-reference (``torch.rand(N, L, device=x.device)``, :750).
+reference (``torch.rand(N, L, device=x.device)``, :750).  A second one: the same methods accept ``sampler``, a
+``fastvim_amd.mae_tokens.MaskSampler`` whose noise is a function of (seed, counter, sample, token) -- made inside the plan
+launch, so no noise tensor exists -- which is what the graph-replayed step (fastvim_amd/mae_step.py) masks with.
 """
 import math
 from functools import partial
@@ -243,17 +245,31 @@ class MaskedAutoencoderViM(nn.Module):
         x = x.permute(0, 5, 1, 3, 2, 4)                 # "nhwpqc->nchpwq"
         return x.reshape(x.shape[0], 3, h * p, h * p)
 
-    def random_masking(self, x, mask_ratio, noise=None):
+    def random_masking(self, x, mask_ratio, noise=None, sampler=None):
         """Per-sample random masking by argsort of uniform noise; the kept ids are sorted ascending because the
         mixers are sequential (models_mamba_faster_mae_vimdecoder.py:738-772)."""
-        return self._masking(x, mask_ratio, noise)[:4]
+        return self._masking(x, mask_ratio, noise, sampler)[:4]
 
-    def _masking(self, x, mask_ratio, noise=None):
+    def _masking(self, x, mask_ratio, noise=None, sampler=None):
         """``random_masking`` plus the step's ``TokenPlan`` as a fifth value: None unless ``fused_tokens`` is set and
         ``mae_tokens.mask_plan_ok`` holds (then the plan's launch replaces the index code and the gather is
-        ``gather_tokens``; same four values)."""
+        ``gather_tokens``; same four values).
+
+        ``sampler`` (a ``mae_tokens.MaskSampler``): the noise is the sampler's, a function of its (seed, counter).  Where
+        the plan's predicate holds the keyed plan launch makes it in registers -- the sampler is the opt-in, whatever
+        ``fused_tokens`` says; elsewhere ``sampler.noise(N, L)`` goes through the code below.  The same masks either way."""
         N, L, D = x.shape
         len_keep = int(L * (1 - mask_ratio))
+        if sampler is not None:
+            if noise is not None:
+                raise ValueError("MaskedAutoencoderViM: noise= and sampler= are two sources of the masking noise; pass one")
+            if (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and D % 4 == 0
+                    and L == int(self.token_size[0]) * int(self.token_size[1])
+                    and mae_tokens.plan_shape_ok(N, self.token_size, len_keep)):
+                plan = mae_tokens.mask_plan_keyed(sampler, N, self.token_size, len_keep, device=x.device)
+                x_masked = mae_tokens.gather_tokens(x, plan.keep_index, plan.restore_index)
+                return x_masked, plan.mask, plan.ids_restore, plan.ids_keep, plan
+            noise = sampler.noise(N, L, device=x.device)
         if noise is None:
             noise = torch.rand(N, L, device=x.device)
         if (self.fused_tokens and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and D % 4 == 0
@@ -282,14 +298,44 @@ class MaskedAutoencoderViM(nn.Module):
         return layer_norm_fn(hidden_states, norm.weight, norm.bias, eps=norm.eps, residual=residual, prenorm=False,
                              residual_in_fp32=self.residual_in_fp32, is_rms_norm=is_rms)
 
-    def forward_encoder(self, x, mask_ratio, inference_params=None, noise=None):
-        return self._encode(x, mask_ratio, inference_params, noise)[:3]
+    def forward_encoder(self, x, mask_ratio, inference_params=None, noise=None, sampler=None):
+        return self._encode(x, mask_ratio, inference_params, noise, sampler)[:3]
 
-    def _encode(self, x, mask_ratio, inference_params=None, noise=None):
+    # ---- the segment protocol of fastvim_amd.mae_step.MAEPretrainStep: what SegmentedTrainStep asks of VisionMamba
+    # (_embed / _run_layers / _final + _head), in MAE form.  The plan carries no gradient and is shared by every run.
+    def _embed_masked(self, imgs, mask_ratio, sampler):
+        """Patch embedding + the masking gather -> (kept tokens, plan).  The keyed plan must apply: a step that cuts the
+        encoder into runs hands the plan from run to run."""
+        x = self.patch_embed(imgs, self.pos_embed)
+        x, _, _, _, plan = self._masking(x, mask_ratio, None, sampler)
+        if plan is None:
+            raise RuntimeError("MaskedAutoencoderViM._embed_masked: the keyed masking plan does not take these tokens "
+                               f"({tuple(x.shape)} {x.dtype}, grid {tuple(self.token_size)}); see mae_tokens.plan_shape_ok")
+        return x, plan
+
+    def _run_layers(self, hidden_states, residual, lo, hi, plan):
+        """Encoder blocks ``lo .. hi - 1`` on the kept tokens."""
+        for layer in self.layers[lo:hi]:
+            hidden_states, residual = layer(hidden_states, residual, plan=plan)
+        return hidden_states, residual
+
+    def _tail(self, hidden_states, residual, imgs, plan):
+        """``norm_f``, the decoder and the reconstruction loss -> (loss, pred)."""
+        latent = self._final_norm(self.norm_f, hidden_states, residual)
+        pred = self.forward_decoder(latent, plan.ids_restore, plan=plan)
+        return self._loss(imgs, pred, plan.mask), pred
+
+    def _loss(self, imgs, pred, mask):
+        table = pixels.pixel_table(self.patch_embed, imgs) if imgs.dtype == torch.uint8 else None
+        if table is None and not self.fused_loss:
+            return self.forward_loss(imgs, pred, mask)
+        return self.reconstruction_loss(imgs, pred, mask, table)
+
+    def _encode(self, x, mask_ratio, inference_params=None, noise=None, sampler=None):
         """``forward_encoder`` plus the step's ``TokenPlan`` (or None) as a fourth value, for ``forward_decoder``."""
         x = self.patch_embed(x, self.pos_embed)
-        if self.fused_tokens:
-            x, mask, ids_restore, ids_keep, plan = self._masking(x, mask_ratio, noise)
+        if self.fused_tokens or sampler is not None:
+            x, mask, ids_restore, ids_keep, plan = self._masking(x, mask_ratio, noise, sampler)
         else:
             (x, mask, ids_restore, ids_keep), plan = self.random_masking(x, mask_ratio, noise), None
         residual = None
@@ -346,20 +392,19 @@ class MaskedAutoencoderViM(nn.Module):
             imgs = pixels.lookup(table, imgs)
         return self.forward_loss(imgs, pred, mask)
 
-    def forward(self, imgs, mask_ratio=0.75, inference_params=None, noise=None):
+    def forward(self, imgs, mask_ratio=0.75, inference_params=None, noise=None, sampler=None):
         """``imgs``: normalised float images, or a uint8 batch once ``fastvim_amd.pixels.attach_pixel_norm`` has put the
-        normalisation table on the model: the patch embedding and the loss then look the pixels up inside their kernels."""
-        table = pixels.pixel_table(self.patch_embed, imgs) if imgs.dtype == torch.uint8 else None
-        latent, mask, ids_restore, plan = self._encode(imgs, mask_ratio, inference_params, noise=noise)
+        normalisation table on the model: the patch embedding and the loss then look the pixels up inside their kernels.
+        ``sampler``: a ``mae_tokens.MaskSampler`` -- the masks of its current (seed, counter), see ``_masking``."""
+        if sampler is None:
+            latent, mask, ids_restore, plan = self._encode(imgs, mask_ratio, inference_params, noise=noise)
+        else:
+            latent, mask, ids_restore, plan = self._encode(imgs, mask_ratio, inference_params, noise=noise, sampler=sampler)
         if plan is None:
             pred = self.forward_decoder(latent, ids_restore, inference_params)
         else:
             pred = self.forward_decoder(latent, ids_restore, inference_params, plan=plan)
-        if table is None and not self.fused_loss:
-            loss = self.forward_loss(imgs, pred, mask)
-        else:
-            loss = self.reconstruction_loss(imgs, pred, mask, table)
-        return loss, pred, mask
+        return self._loss(imgs, pred, mask), pred, mask
 
 
 def _mae(embed_dim, depth, patch_size, stride, kwargs):

@@ -26,6 +26,29 @@ import torch.distributed as dist
 from . import pixels
 
 
+def snapshot_training_state(flat, opt):
+    """What the warm-up steps of a capture may advance, cloned: (buffers, CPU RNG state, GPU RNG state, device) for
+    ``restore_training_state`` (``SegmentedTrainStep`` and ``fastvim_amd.mae_step.MAEPretrainStep``)."""
+    f, o = flat, opt
+    # every tensor attribute of the optimizer (moments, EMA, step count, lr, decay mask, ...) and the state's own buffers:
+    # whatever a warm-up step may advance is put back, not a hand-picked list
+    bufs = [f.param_flat, f.shadow_flat] + list(getattr(f, "_t_dst", [])) + list(getattr(f, "_tx_dst", [])) + list(getattr(f, "_pk_dst", []))   # (+ the transposed in_proj / x_proj shadows and the fragment-major copies)
+    for v in vars(o).values():
+        if torch.is_tensor(v) and v.is_cuda and all(v is not b for b in bufs):
+            bufs.append(v)
+    dev = f.param_flat.device
+    return [(b, b.clone()) for b in bufs], torch.get_rng_state(), torch.cuda.get_rng_state(dev), dev
+
+
+def restore_training_state(snap):
+    bufs, cpu_rng, gpu_rng, dev = snap
+    with torch.no_grad():
+        for b, saved in bufs:
+            b.copy_(saved)
+    torch.set_rng_state(cpu_rng)
+    torch.cuda.set_rng_state(gpu_rng, dev)
+
+
 class SegmentedTrainStep:
     """``model`` must expose ``_embed / _run_layers / _final / _head`` (fastvim_amd.fastvim.VisionMamba).
     ``loss_fn(logits, target) -> scalar``.  ``x`` / ``target`` are the static input buffers the graphs read; copy
@@ -184,24 +207,11 @@ class SegmentedTrainStep:
         return loss
 
     def _snapshot(self):
-        f, o = self.flat, self.opt
-        # every tensor attribute of the optimizer (moments, EMA, step count, lr, decay mask, ...) and the state's own buffers:
-        # whatever a warm-up step may advance is put back, not a hand-picked list
-        bufs = [f.param_flat, f.shadow_flat] + list(getattr(f, "_t_dst", [])) + list(getattr(f, "_tx_dst", [])) + list(getattr(f, "_pk_dst", []))   # (+ the transposed in_proj / x_proj shadows and the fragment-major copies)
-        for v in vars(o).values():
-            if torch.is_tensor(v) and v.is_cuda and all(v is not b for b in bufs):
-                bufs.append(v)
-        dev = f.param_flat.device
-        return ([(b, b.clone()) for b in bufs], torch.get_rng_state(), torch.cuda.get_rng_state(dev), dev,
-                None if self.hcs is None else self.hcs.last())
+        return (*snapshot_training_state(self.flat, self.opt), None if self.hcs is None else self.hcs.last())
 
     def _restore(self, snap, sampler=True):
-        bufs, cpu_rng, gpu_rng, dev, subset = snap
-        with torch.no_grad():
-            for b, saved in bufs:
-                b.copy_(saved)
-        torch.set_rng_state(cpu_rng)
-        torch.cuda.set_rng_state(gpu_rng, dev)
+        restore_training_state(snap[:4])
+        subset = snap[4]
         if subset is not None and sampler:
             self.hcs.set(subset)
 

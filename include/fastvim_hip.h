@@ -85,7 +85,10 @@ const char* fv_last_error(void);
  *      (RandAugment of planar uint8 batches on the device, bit-exact to PIL); no existing entry point changed.
  *      Later, still 3: fv_jpeg_probe, fv_jpeg_entropy_decode, fv_jpeg_table_ints, fv_jpeg_idct and fv_jpeg_rgb were ADDED
  *      (JPEG decode split between a host entropy decoder and two device launches, byte-exact to PIL); no existing entry
- *      point changed. */
+ *      point changed.
+ *      Later, still 3: fv_mae_noise and fv_mae_mask_plan_keyed were ADDED (the MAE masking noise as a function of a key
+ *      block in device memory, and the masking plan of that noise without the noise tensor); fv_mae_mask_plan is
+ *      unchanged. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -1045,6 +1048,15 @@ int fv_mae_loss_bwd(const void* img, const float* table, const void* pred, int p
  *   (n_partials = ceil(B L / FV_MAE_DECODER_ROWS_PER_BLOCK) rows of dim doubles, caller-allocated), a second launch adds
  *   those.  No atomics: the same inputs give the same bits.  restore_index must hold each of 0 .. K-1 once per sample (as
  *   fv_mae_mask_plan writes it) for every row of dx to be written.
+ *
+ * The KEY BLOCK: int32[4] in DEVICE memory, (k0, k1, step_lo, step_hi), read when the kernels RUN (a replayed graph takes
+ *   the values of that moment).  The masking noise of sample b, token l is u = float(w >> 8) * 2^-24 -- exact, in [0, 1),
+ *   24 bits like torch.rand -- with w = word (l & 3) of Philox4x32-10 under key (k0, k1) and counter (l >> 2, b, step_lo,
+ *   step_hi); the rounds are those of the erase noise (fv_random_erase).
+ * fv_mae_noise: noise (batch, len) fp32 = that u for every (b, l): one launch.
+ * fv_mae_mask_plan_keyed: fv_mae_mask_plan of the noise of `block` with the noise made inside the launch -- no (B, L)
+ *   tensor exists; same outputs, same limits, same stable order, and every output equal bit for bit to fv_mae_mask_plan
+ *   on what fv_mae_noise(block, ., batch, grid_h grid_w) writes.
  * Alignment: every buffer that of its element type only.
  * ---------------------------------------------------------------------- */
 #define FV_MAE_PLAN_MAX_TOKENS 1024
@@ -1053,6 +1065,11 @@ int fv_mae_mask_plan(const float* noise, long long* ids_keep, long long* ids_res
                      int* restore_index, int* row_index_even, long long* ids_keep_odd, long long* order, long long* inverse,
                      int* order_index, int* inverse_index, int* row_index_odd, int batch, int grid_h, int grid_w,
                      int len_keep, fv_stream_t stream);
+int fv_mae_noise(const int32_t* block, float* noise, int batch, int len, fv_stream_t stream);
+int fv_mae_mask_plan_keyed(const int32_t* block, long long* ids_keep, long long* ids_restore, float* mask, int* keep_index,
+                           int* restore_index, int* row_index_even, long long* ids_keep_odd, long long* order,
+                           long long* inverse, int* order_index, int* inverse_index, int* row_index_odd, int batch,
+                           int grid_h, int grid_w, int len_keep, fv_stream_t stream);
 int fv_tokens_gather(const void* in, int in_dtype, const int* index, void* out, int out_dtype, int batch, int len_in,
                      int len_out, int dim, fv_stream_t stream);
 int fv_mae_decoder_tokens_fwd(const void* x, int x_dtype, const float* mask_token, const float* pos_embed,
