@@ -45,6 +45,7 @@ C_ABI_SYMBOLS = (
     "fv_resample_u8_ok", "fv_resample_workspace_ints", "fv_resample_coeffs", "fv_resample_u8",
     "fv_randaug_ok", "fv_randaug_workspace_bytes", "fv_randaug_stats", "fv_randaug_apply",
     "fv_jpeg_probe", "fv_jpeg_entropy_decode", "fv_jpeg_table_ints", "fv_jpeg_idct", "fv_jpeg_rgb",
+    "fv_jpeg_packed_bound", "fv_jpeg_entropy_decode_packed", "fv_jpeg_idct_packed",
     "fv_mae_noise", "fv_mae_mask_plan_keyed",
 )
 
@@ -97,13 +98,14 @@ def lib():
         cdll.fv_resample_workspace_ints.restype = ctypes.c_longlong
         cdll.fv_randaug_workspace_bytes.restype = ctypes.c_longlong
         cdll.fv_jpeg_table_ints.restype = ctypes.c_longlong
+        cdll.fv_jpeg_packed_bound.restype = ctypes.c_longlong
         _lib = _DeviceGuarded(cdll)
     return _lib
 
 
 def host_lib():
-    """The bare CDLL, for the library's HOST-only entry points (``fv_jpeg_probe``, ``fv_jpeg_entropy_decode``): no device
-    guard, no GPU needed.  ctypes releases the GIL for the length of a call."""
+    """The bare CDLL, for the library's HOST-only entry points (``fv_jpeg_probe``, ``fv_jpeg_entropy_decode`` and its packed
+    form): no device guard, no GPU needed.  ctypes releases the GIL for the length of a call."""
     return lib()._cdll
 
 

@@ -10,6 +10,11 @@
 //                     blocks of a 32-lane half fall on 32 distinct banks).  Lane r stores pixel row r as one 8-byte
 //                     store.  A block whose AC terms are all zero -- most blocks of a photograph -- skips LDS and both
 //                     passes: pass 1 gives 4 dc exactly, pass 2 (dc + 4) >> 3.
+//                     Two forms of the coefficients, one kernel body (PACKED): the dense form above, and the packed form
+//                     -- a 16-byte header per block (64-bit mask of the non-zero AC terms, value offset, `wide`, DC) and
+//                     the non-zero values as int8 or int16.  Lane r owns mask byte r: its values start at number
+//                     popcount(mask below bit 8 r) of the block; it loads the aligned words around them without a
+//                     branch and shifts the values out; DC-only is mask == 0.
 //   jpeg_rgb_kernel   a thread per QUAD of four consecutive pixels of a crop (12 bytes: three aligned 4-byte stores).
 // Both split the table's prefix sums into one contiguous share per workgroup: the grid depends on capacities only, so a
 // captured launch serves whatever batch the table describes when it runs.
@@ -43,11 +48,13 @@ struct Geo {
   int nblk[3];
 };
 
-// the record's geometry; false: not a JPEG job or not a record the decoder writes
-__device__ __forceinline__ bool geometry(const int* r, long long cap, Geo& g) {
+constexpr int KIND_DENSE = 1 << 1, KIND_PACKED = 1 << 2;      // record[0] as a bit
+
+// the record's geometry; false: not a JPEG job of one of `kinds` or not a record the decoder writes
+__device__ __forceinline__ bool geometry(const int* r, int kinds, long long cap, Geo& g) {
   g.ncomp = r[3]; g.cls = r[4];
   g.x0 = r[5]; g.y0 = r[6]; g.mw = r[7]; g.mh = r[8];
-  if (r[0] != 1 || g.cls < 0 || g.cls > 3 || g.ncomp != (g.cls == FV_JPEG_GRAY ? 1 : 3)) return false;
+  if (r[0] < 1 || r[0] > 2 || !((kinds >> r[0]) & 1) || g.cls < 0 || g.cls > 3 || g.ncomp != (g.cls == FV_JPEG_GRAY ? 1 : 3)) return false;
   if (g.x0 < 0 || g.y0 < 0 || g.mw < 1 || g.mh < 1 || g.x0 > JP_MAX_MCUS - g.mw || g.y0 > JP_MAX_MCUS - g.mh) return false;
   g.hmax = (g.cls == FV_JPEG_422 || g.cls == FV_JPEG_420) ? 2 : 1;
   g.vmax = g.cls == FV_JPEG_420 ? 2 : 1;
@@ -86,14 +93,16 @@ __device__ __forceinline__ void idct8(const int (&in)[8], int (&o)[8], int shift
 
 __device__ __forceinline__ unsigned clamp8(int v) { return (unsigned)(v < 0 ? 0 : v > 255 ? 255 : v); }
 
-__global__ __launch_bounds__(JP_THREADS) void jpeg_idct_kernel(const int16_t* __restrict__ coef, long long coef_elems,
+// `src_cap` counts int16 elements of the dense form, bytes of the packed one
+template <bool PACKED>
+__global__ __launch_bounds__(JP_THREADS) void jpeg_idct_kernel(const void* __restrict__ src, long long src_cap,
                                                                 const int* __restrict__ table, uint8_t* __restrict__ planes,
                                                                 long long plane_bytes, int batch) {
   __shared__ int lds[JP_BLOCKS][8 * JP_ROW];
   const int* pre = table + (long long)batch * REC;
   const long long total = pre[batch];
   const int slot = threadIdx.x >> 3, l8 = threadIdx.x & 7;
-  const long long cap = coef_elems < plane_bytes ? coef_elems : plane_bytes;
+  const long long cap = PACKED ? plane_bytes : src_cap < plane_bytes ? src_cap : plane_bytes;
   // a workgroup takes one CONTIGUOUS share of the blocks: its sample is searched once and then walked, a step at most
   // every few passes (uniform in the workgroup)
   const long long share = ((total + gridDim.x - 1) / gridDim.x + JP_BLOCKS - 1) / JP_BLOCKS * JP_BLOCKS;
@@ -104,6 +113,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_idct_kernel(const int16_t* __
     const long long gb = base + slot;
     bool valid = gb < last;
     int x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long mask = 0;                   // PACKED: the block's non-zero AC terms
     long long dst = 0;       // byte offset of this lane's pixel row in the plane workspace
     if (valid) {
       int s = s0;
@@ -111,7 +121,8 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_idct_kernel(const int16_t* __
       const int* r = table + (long long)s * REC;
       Geo g;
       long long lb = gb - pre[s];
-      valid = geometry(r, cap, g) && lb >= 0;
+      const long long ls = lb;                     // the block's number in the sample
+      valid = geometry(r, PACKED ? KIND_PACKED : KIND_DENSE, cap, g) && lb >= 0;
       int c = 0;             // the block's component; no runtime index into g.nblk / g.off (they stay in registers)
       if (valid && lb >= g.nblk[0]) {
         lb -= g.nblk[0];
@@ -126,19 +137,71 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_idct_kernel(const int16_t* __
         const long long off = c == 0 ? g.off[0] : c == 1 ? g.off[1] : g.off[2];
         const int bw = g.mw * (c == 0 ? g.hmax : 1);
         const int brow = (int)lb / bw, bcol = (int)lb % bw;
-        const int4 cv = *reinterpret_cast<const int4*>(coef + off + lb * 64 + l8 * 8);
         const int4 q0 = *reinterpret_cast<const int4*>(r + 32 + 64 * c + l8 * 8);
         const int4 q1 = *reinterpret_cast<const int4*>(r + 36 + 64 * c + l8 * 8);
-        x[0] = (int)(int16_t)(cv.x & 0xffff) * q0.x; x[1] = (cv.x >> 16) * q0.y;
-        x[2] = (int)(int16_t)(cv.y & 0xffff) * q0.z; x[3] = (cv.y >> 16) * q0.w;
-        x[4] = (int)(int16_t)(cv.z & 0xffff) * q1.x; x[5] = (cv.z >> 16) * q1.y;
-        x[6] = (int)(int16_t)(cv.w & 0xffff) * q1.z; x[7] = (cv.w >> 16) * q1.w;
+        if constexpr (PACKED) {
+          // header and values, every byte of them inside [0, src_cap); a block that does not fit is skipped
+          const uint8_t* pool = static_cast<const uint8_t*>(src);
+          const long long hb = rec_i64(r, 25), vb = rec_i64(r, 27);
+          valid = hb >= 0 && (hb & 15) == 0 && vb >= 0 && (vb & 1) == 0 && vb <= src_cap && hb <= src_cap - 16 * (ls + 1);
+          if (valid) {
+            const uint4 h = *reinterpret_cast<const uint4*>(pool + hb + 16 * ls);
+            const unsigned long long m = ((unsigned long long)h.y << 32 | h.x) & ~1ull;
+            const int wide = (int)(h.z >> 31);
+            const long long vo = vb + (long long)(h.z & 0x7fffffffu);
+            // values are read as whole aligned words: they have to lie inside the pool's whole words
+            const long long cap4 = src_cap & ~3ll;
+            valid = (h.z & 1u) == 0 && vo <= cap4 - ((long long)__popcll(m) << wide);
+            if (valid) {
+              mask = m;
+              const int q[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+              const unsigned m8 = (unsigned)(m >> (8 * l8)) & 0xffu;
+              // this lane's values: at most 8 (16 bytes) from byte a on.  Five aligned words cover them at any a; all five
+              // are loaded without a branch -- one round trip -- and a word past the pool's last is replaced by the last
+              // (cap4 >= 16: the header fitted), which no value of this lane lies in
+              const long long a = vo + ((long long)__popcll(m & ((1ull << (8 * l8)) - 1ull)) << wide);
+              unsigned d[5];
+#pragma unroll
+              for (int i = 0; i < 5; ++i) {
+                const long long at = (a & ~3ll) + 4 * i;
+                d[i] = *reinterpret_cast<const unsigned*>(pool + (at > cap4 - 4 ? cap4 - 4 : at));
+              }
+              const unsigned sh = 8u * ((unsigned)a & 3u);
+              unsigned w[4];
+#pragma unroll
+              for (int i = 0; i < 4; ++i) w[i] = (unsigned)((((unsigned long long)d[i + 1] << 32) | d[i]) >> sh);
+              unsigned long long lo = (unsigned long long)w[1] << 32 | w[0], hi = (unsigned long long)w[3] << 32 | w[2];
+              const unsigned step = wide ? 16u : 8u;
+#pragma unroll
+              for (int j = 0; j < 8; ++j) {
+                const int v = wide ? (int)(int16_t)(lo & 0xffffu) : (int)(int8_t)(lo & 0xffu);
+                if ((m8 >> j) & 1u) {
+                  x[j] = v * q[j];
+                  lo = (lo >> step) | (hi << (64u - step));
+                  hi >>= step;
+                }
+              }
+              if (l8 == 0) x[0] = (int)(int16_t)(h.w & 0xffffu) * q[0];
+            }
+          }
+        } else {
+          const int4 cv = *reinterpret_cast<const int4*>(static_cast<const int16_t*>(src) + off + lb * 64 + l8 * 8);
+          x[0] = (int)(int16_t)(cv.x & 0xffff) * q0.x; x[1] = (cv.x >> 16) * q0.y;
+          x[2] = (int)(int16_t)(cv.y & 0xffff) * q0.z; x[3] = (cv.y >> 16) * q0.w;
+          x[4] = (int)(int16_t)(cv.z & 0xffff) * q1.x; x[5] = (cv.z >> 16) * q1.y;
+          x[6] = (int)(int16_t)(cv.w & 0xffff) * q1.z; x[7] = (cv.w >> 16) * q1.w;
+        }
         dst = off + ((long long)brow * 8 + l8) * ((long long)bw * 8) + (long long)bcol * 8;
       }
     }
-    const int ac = (l8 == 0 ? 0 : x[0]) | x[1] | x[2] | x[3] | x[4] | x[5] | x[6] | x[7];
-    const unsigned long long any_ac = __ballot(valid && ac != 0);
-    const bool dc_only = ((any_ac >> ((threadIdx.x & 63) & ~7)) & 0xffull) == 0;
+    bool dc_only;
+    if constexpr (PACKED) {
+      dc_only = mask == 0;                        // known from the header; the same for the 8 lanes of a block
+    } else {
+      const int ac = (l8 == 0 ? 0 : x[0]) | x[1] | x[2] | x[3] | x[4] | x[5] | x[6] | x[7];
+      const unsigned long long any_ac = __ballot(valid && ac != 0);
+      dc_only = ((any_ac >> ((threadIdx.x & 63) & ~7)) & 0xffull) == 0;
+    }
     const int dc = __shfl(x[0], 0, 8);
     const bool full = valid && !dc_only;
     int* blk = lds[slot];
@@ -198,7 +261,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_rgb_kernel(const uint8_t* __r
     while (s < batch - 1 && (long long)pre[s + 1] <= gq) ++s;
     const int* r = table + (long long)s * REC;
     Geo g;
-    if (!geometry(r, plane_bytes, g)) continue;
+    if (!geometry(r, KIND_DENSE | KIND_PACKED, plane_bytes, g)) continue;
     const int H = r[1], W = r[2], top = r[19], left = r[20], ch = r[21], cw = r[22];
     if (H < 1 || W < 1 || H > 65535 || W > 65535 || top < 0 || left < 0 || ch < 1 || cw < 1 || top > H - ch || left > W - cw) continue;
     const long long npx = (long long)ch * cw, poff = rec_i64(r, 23);
@@ -288,8 +351,23 @@ extern "C" int fv_jpeg_idct(const void* coef, long long coef_elems, const int* t
   FV_CHECK(((uintptr_t)coef & 15) == 0 && ((uintptr_t)table & 15) == 0 && ((uintptr_t)planes & 7) == 0,
            "jpeg_idct: misaligned buffer (coefficients and table 16 bytes, planes 8)");
   const long long cap = coef_elems < plane_bytes ? coef_elems : plane_bytes;
-  hipLaunchKernelGGL(jpeg_idct_kernel, dim3(stride_grid(cap / 64, JP_BLOCKS)), dim3(JP_THREADS), 0, (hipStream_t)stream,
-                     (const int16_t*)coef, coef_elems, table, (uint8_t*)planes, plane_bytes, batch);
+  hipLaunchKernelGGL(jpeg_idct_kernel<false>, dim3(stride_grid(cap / 64, JP_BLOCKS)), dim3(JP_THREADS), 0, (hipStream_t)stream,
+                     coef, coef_elems, table, (uint8_t*)planes, plane_bytes, batch);
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
+extern "C" int fv_jpeg_idct_packed(const void* pool, long long pool_bytes, const int* table, void* planes,
+                                   long long plane_bytes, int batch, fv_stream_t stream) {
+  FV_CHECK(pool && table && planes, "jpeg_idct_packed: null pointer");
+  FV_CHECK(batch_ok(batch), "jpeg_idct_packed: batch %d outside [1, 4096]", batch);
+  FV_CHECK(pool_bytes >= 0 && plane_bytes >= 0, "jpeg_idct_packed: negative capacity");
+  FV_CHECK(((uintptr_t)pool & 15) == 0 && ((uintptr_t)table & 15) == 0 && ((uintptr_t)planes & 7) == 0,
+           "jpeg_idct_packed: misaligned buffer (pool and table 16 bytes, planes 8)");
+  // a block takes a 16-byte header and 64 plane bytes at the least
+  const long long cap = pool_bytes / 16 < plane_bytes / 64 ? pool_bytes / 16 : plane_bytes / 64;
+  hipLaunchKernelGGL(jpeg_idct_kernel<true>, dim3(stride_grid(cap, JP_BLOCKS)), dim3(JP_THREADS), 0, (hipStream_t)stream, pool,
+                     pool_bytes, table, (uint8_t*)planes, plane_bytes, batch);
   FV_LAUNCH_CHECK();
   return FV_OK;
 }

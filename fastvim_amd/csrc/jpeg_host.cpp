@@ -1,13 +1,15 @@
 // The host half of the JPEG decode (include/fastvim_hip.h at fv_jpeg_probe): marker parser and Huffman decoder of baseline
 // JPEG files, plain C++ with nothing from HIP -- the file also compiles on its own with the host compiler
-// (tools/jpeg_host_check.cpp runs it under the address and undefined-behaviour sanitizers).  No global state: any number
-// of loader threads may decode at once.  Every read is checked against [data, data + nbytes), every write against
+// (tools/jpeg_host_check.cpp and tools/jpeg_packed_check.cpp run it under the address and undefined-behaviour
+// sanitizers).  No shared state -- the packed entry point keeps a scratch buffer per thread: any number of loader threads
+// may decode at once.  Every read is checked against [data, data + nbytes), every write against
 // coef_out[0 : coef_capacity]; an anomaly is an error code, never a partial result.
 //
 // The decoder is the shape of libjpeg's jdhuff.c: a 64-bit bit buffer filled a byte at a time (0xFF 0x00 unstuffed, fill
 // 0xFF bytes skipped, a marker stops the fill and zero bits follow), and a lookahead table of LOOK bits that gives
 // length and symbol of every code that short in one probe; longer codes walk maxcode[].
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/fastvim_hip.h"
@@ -251,47 +253,35 @@ inline int symbol(Bits& b, const Huff& h) {
   return h.vals[idx];
 }
 
-}  // namespace
+// The window's geometry: the offset of each component's first block (in blocks) and the blocks of the window.
+struct Window {
+  int x0, y0, mw, mh;
+  long long first[3] = {0, 0, 0}, blocks = 0;
+};
 
-extern "C" int fv_jpeg_probe(const void* data, long long nbytes, int* info) {
-  if (!data || !info || nbytes < 0) return FV_ERR_INVALID;
-  Frame f;
-  parse((const uint8_t*)data, nbytes, f);
-  const bool ok = f.reason == FV_JPEG_R_OK;
-  info[0] = f.H;
-  info[1] = f.W;
-  info[2] = f.ncomp;
-  info[3] = ok ? f.cls : -1;
-  info[4] = ok ? 1 : 0;
-  info[5] = f.reason;
-  info[6] = ok ? f.mcus_x : 0;
-  info[7] = ok ? f.mcus_y : 0;
-  return FV_OK;
+int window_of(const Frame& f, const int* window, Window& w) {
+  w.x0 = window[0]; w.y0 = window[1]; w.mw = window[2]; w.mh = window[3];
+  if (w.x0 < 0 || w.y0 < 0 || w.mw < 1 || w.mh < 1 || w.x0 > f.mcus_x - w.mw || w.y0 > f.mcus_y - w.mh) return FV_JPEG_E_WINDOW;
+  for (int c = 0; c < f.ncomp; ++c) {
+    w.first[c] = w.blocks;
+    w.blocks += (long long)w.mw * f.ch[c] * w.mh * f.cv[c];
+  }
+  return w.blocks > 0x7fffffff ? FV_JPEG_E_CAPACITY : FV_OK;
 }
 
-extern "C" int fv_jpeg_entropy_decode(const void* data, long long nbytes, const int* window, int16_t* coef_out,
-                                      long long coef_capacity, int* record) {
-  if (!data || !window || !coef_out || !record || nbytes < 0 || coef_capacity < 0) return FV_ERR_INVALID;
-  Frame f;
-  parse((const uint8_t*)data, nbytes, f);
-  if (f.reason != FV_JPEG_R_OK) return FV_JPEG_E_UNSERVED;
-  const int x0 = window[0], y0 = window[1], mw = window[2], mh = window[3];
-  if (x0 < 0 || y0 < 0 || mw < 1 || mh < 1 || x0 > f.mcus_x - mw || y0 > f.mcus_y - mh) return FV_JPEG_E_WINDOW;
-  const int nc = f.ncomp;
-  long long off[3] = {0, 0, 0}, total = 0, blocks = 0;
-  for (int c = 0; c < nc; ++c) {
-    off[c] = total;
-    const long long nb = (long long)mw * f.ch[c] * mh * f.cv[c];
-    blocks += nb;
-    total += nb * 64;
-  }
-  if (total > coef_capacity || blocks > 0x7fffffff) return FV_JPEG_E_CAPACITY;
-
-  Bits b{(const uint8_t*)data, nbytes, f.scan};
+// The MCU loop of both entry points: MCUs in file order up to the last one the window needs; the 64 coefficients of a
+// block inside the window go, natural order, to coef_out + 64 * (its number), every other block to a scratch block.
+// With `masks` (one word per block of the window, or null) the block's word gets bit k set for every AC term k written --
+// an AC term that is coded is never 0 -- and bit 0 when one of them lies outside -128 .. 127.  `mcus` is the count decoded.
+int decode_mcus(const Frame& f, const uint8_t* data, long long nbytes, const Window& w, int16_t* coef_out,
+                long long coef_capacity, uint64_t* masks, long long* mcus) {
+  const int x0 = w.x0, y0 = w.y0, mw = w.mw, mh = w.mh, nc = f.ncomp;
+  Bits b{data, nbytes, f.scan};
   int pred[3] = {0, 0, 0};
   const long long last = (long long)(y0 + mh - 1) * f.mcus_x + x0 + mw - 1;
   int mx = 0, my = 0, to_restart = f.ri, rst = 0;
   int16_t skipped[64];
+  uint64_t skipped_mask;
   for (long long m = 0; m <= last; ++m) {
     if (f.ri && m && to_restart == 0) {
       // byte-align; a whole data byte left over is not what an encoder writes
@@ -322,11 +312,14 @@ extern "C" int fv_jpeg_entropy_decode(const void* data, long long nbytes, const 
       for (int by = 0; by < v; ++by)
         for (int bx = 0; bx < h; ++bx) {
           int16_t* blk = skipped;
+          uint64_t* bits = &skipped_mask;
           if (inside) {
-            const long long e = off[c] + (((long long)(my - y0) * v + by) * ((long long)mw * h) + (long long)(mx - x0) * h + bx) * 64;
+            const long long e = (w.first[c] + ((long long)(my - y0) * v + by) * ((long long)mw * h) + (long long)(mx - x0) * h + bx) * 64;
             if (e < 0 || e + 64 > coef_capacity) return FV_JPEG_E_CAPACITY;
             blk = coef_out + e;
+            if (masks) bits = masks + e / 64;
           }
+          uint64_t mask = 0;
           memset(blk, 0, 128);
           if (b.bits < 32) b.fill();
           int s = symbol(b, dc);
@@ -342,7 +335,9 @@ extern "C" int fv_jpeg_entropy_decode(const void* data, long long nbytes, const 
             if (s) {
               k += r;
               if (k > 63) return FV_JPEG_E_RUN;
-              blk[kZigzag[k]] = (int16_t)extend((int)b.get(s), s);
+              const int at = kZigzag[k], v = extend((int)b.get(s), s);
+              blk[at] = (int16_t)v;
+              mask |= (uint64_t)1 << at | (uint64_t)((unsigned)(v + 128) > 255u);
               ++k;
             } else if (r == 15) {
               k += 16;
@@ -352,26 +347,141 @@ extern "C" int fv_jpeg_entropy_decode(const void* data, long long nbytes, const 
             }
           }
           if (b.real < 0) return FV_JPEG_E_TRUNCATED;
+          *bits = mask;
         }
     }
     if (++mx == f.mcus_x) { mx = 0; ++my; }
   }
+  *mcus = last + 1;
+  return FV_OK;
+}
 
+// the words of the record both forms share
+void common_record(const Frame& f, const Window& w, long long mcus, int kind, int* record) {
   memset(record, 0, sizeof(int) * FV_JPEG_REC_INTS);
-  record[0] = 1;
+  record[0] = kind;
   record[1] = f.H;
   record[2] = f.W;
-  record[3] = nc;
+  record[3] = f.ncomp;
   record[4] = f.cls;
-  record[5] = x0; record[6] = y0; record[7] = mw; record[8] = mh;
-  for (int c = 0; c < nc; ++c) {
-    record[9 + 2 * c] = (int)(uint32_t)(off[c] & 0xffffffffll);
-    record[10 + 2 * c] = (int)(off[c] >> 32);
+  record[5] = w.x0; record[6] = w.y0; record[7] = w.mw; record[8] = w.mh;
+  for (int c = 0; c < f.ncomp; ++c) {
+    const long long off = w.first[c] * 64;       // dense: elements of the coefficients; both: bytes of the plane
+    record[9 + 2 * c] = (int)(uint32_t)(off & 0xffffffffll);
+    record[10 + 2 * c] = (int)(off >> 32);
     for (int k = 0; k < 64; ++k) record[32 + 64 * c + k] = f.qt[f.ctq[c]][k];
   }
-  record[15] = (int)(uint32_t)(total & 0xffffffffll);
-  record[16] = (int)(total >> 32);
-  record[17] = (int)blocks;
-  record[18] = (int)(last + 1 > 0x7fffffff ? 0x7fffffff : last + 1);
+  record[17] = (int)w.blocks;
+  record[18] = (int)(mcus > 0x7fffffff ? 0x7fffffff : mcus);
+}
+
+// the packed entry point's dense window: kept per thread from call to call unless a single file made it large
+struct Scratch {
+  void* p = nullptr;
+  size_t n = 0;
+  ~Scratch() { free(p); }
+  void* get(size_t need) {
+    if (need > n) {
+      free(p);
+      p = malloc(need);
+      n = p ? need : 0;
+    }
+    return p;
+  }
+  void trim() {
+    if (n > ((size_t)16 << 20)) { free(p); p = nullptr; n = 0; }
+  }
+};
+thread_local Scratch scratch;
+
+inline void put_i64(int* record, int at, long long v) {
+  record[at] = (int)(uint32_t)(v & 0xffffffffll);
+  record[at + 1] = (int)(v >> 32);
+}
+
+}  // namespace
+
+extern "C" int fv_jpeg_probe(const void* data, long long nbytes, int* info) {
+  if (!data || !info || nbytes < 0) return FV_ERR_INVALID;
+  Frame f;
+  parse((const uint8_t*)data, nbytes, f);
+  const bool ok = f.reason == FV_JPEG_R_OK;
+  info[0] = f.H;
+  info[1] = f.W;
+  info[2] = f.ncomp;
+  info[3] = ok ? f.cls : -1;
+  info[4] = ok ? 1 : 0;
+  info[5] = f.reason;
+  info[6] = ok ? f.mcus_x : 0;
+  info[7] = ok ? f.mcus_y : 0;
+  return FV_OK;
+}
+
+extern "C" int fv_jpeg_entropy_decode(const void* data, long long nbytes, const int* window, int16_t* coef_out,
+                                      long long coef_capacity, int* record) {
+  if (!data || !window || !coef_out || !record || nbytes < 0 || coef_capacity < 0) return FV_ERR_INVALID;
+  Frame f;
+  parse((const uint8_t*)data, nbytes, f);
+  if (f.reason != FV_JPEG_R_OK) return FV_JPEG_E_UNSERVED;
+  Window w;
+  int rc = window_of(f, window, w);
+  if (rc != FV_OK) return rc;
+  const long long total = w.blocks * 64;
+  if (total > coef_capacity) return FV_JPEG_E_CAPACITY;
+  long long mcus = 0;
+  rc = decode_mcus(f, (const uint8_t*)data, nbytes, w, coef_out, coef_capacity, nullptr, &mcus);
+  if (rc != FV_OK) return rc;
+  common_record(f, w, mcus, 1, record);
+  put_i64(record, 15, total);
+  return FV_OK;
+}
+
+extern "C" long long fv_jpeg_packed_bound(long long blocks) { return blocks > 0 ? blocks * (16 + 126) : 0; }
+
+// The packed form (include/fastvim_hip.h): the MCU loop above decodes into a dense scratch of the window and notes each
+// block's mask -- the file interleaves the components, the packed values are in block order -- and one pass over the
+// masks writes headers and values.
+extern "C" int fv_jpeg_entropy_decode_packed(const void* data, long long nbytes, const int* window, void* out,
+                                             long long out_capacity_bytes, int* record) {
+  if (!data || !window || !out || !record || nbytes < 0 || out_capacity_bytes < 0 || ((uintptr_t)out & 15)) return FV_ERR_INVALID;
+  Frame f;
+  parse((const uint8_t*)data, nbytes, f);
+  if (f.reason != FV_JPEG_R_OK) return FV_JPEG_E_UNSERVED;
+  Window w;
+  int rc = window_of(f, window, w);
+  if (rc != FV_OK) return rc;
+  const long long vbase = 16 * w.blocks;
+  if (vbase > out_capacity_bytes) return FV_JPEG_E_CAPACITY;      // also bounds the scratch: 8 x the capacity
+  uint64_t* masks = (uint64_t*)scratch.get((size_t)w.blocks * (8 + 128));
+  if (!masks) return FV_JPEG_E_CAPACITY;
+  const int16_t* dense = (const int16_t*)(masks + w.blocks);
+  long long mcus = 0;
+  rc = decode_mcus(f, (const uint8_t*)data, nbytes, w, (int16_t*)(masks + w.blocks), w.blocks * 64, masks, &mcus);
+  uint8_t* const o = (uint8_t*)out;
+  long long cur = vbase;                                           // where the next block's values go; cur - vbase is even
+  for (long long blk = 0; rc == FV_OK && blk < w.blocks; ++blk) {
+    const int16_t* t = dense + blk * 64;
+    const uint64_t mask = masks[blk] & ~(uint64_t)1;
+    const bool wide = masks[blk] & 1;
+    const int n = __builtin_popcountll(mask), bytes = wide ? 2 * n : n;
+    if (cur - vbase > 0x7fffffff || cur + bytes + (bytes & 1) > out_capacity_bytes) { rc = FV_JPEG_E_CAPACITY; break; }
+    const uint32_t hdr[4] = {(uint32_t)mask, (uint32_t)(mask >> 32), (uint32_t)(cur - vbase) | (wide ? 0x80000000u : 0u),
+                             (uint32_t)(uint16_t)t[0]};
+    memcpy(o + 16 * blk, hdr, 16);                                 // little-endian host, as the device
+    uint8_t* v8 = o + cur;
+    if (wide) {
+      for (uint64_t m = mask; m; m &= m - 1, v8 += 2) memcpy(v8, t + __builtin_ctzll(m), 2);
+    } else {
+      for (uint64_t m = mask; m; m &= m - 1) *v8++ = (uint8_t)(int8_t)t[__builtin_ctzll(m)];
+    }
+    if (bytes & 1) *v8++ = 0;
+    cur = v8 - o;
+  }
+  scratch.trim();
+  if (rc != FV_OK) return rc;
+  common_record(f, w, mcus, 2, record);
+  put_i64(record, 15, cur);
+  put_i64(record, 25, 0);
+  put_i64(record, 27, vbase);
   return FV_OK;
 }

@@ -13,6 +13,9 @@ launches run unchanged on it::
 
 Only the MCUs the crop needs are kept (``mcu_window``), and Huffman decoding stops after the last of them.  The staged
 form is dense int16 coefficients, about 3 bytes per window pixel at 4:2:0 -- the order of the RGB crop it replaces.
+``JpegImageStage(..., coef_format="packed")`` stages the PACKED form instead (include/fastvim_hip.h: per block a 64-bit
+mask of its non-zero AC terms and those values as int8 or int16), a fifth to a third of the dense bytes on the files
+measured in DESIGN.md; ``unpack`` restates the format in numpy.
 
 Served: baseline (SOF0) 8-bit Huffman files with one interleaved scan; grayscale, or YCbCr at 4:4:4, 4:2:2 (2x1) or 4:2:0
 (2x2).  A file outside that (progressive, arithmetic, 12-bit, CMYK, RGB-coded, other sampling, several scans, 16-bit
@@ -85,15 +88,75 @@ def window_elements(subsampling, window):
     return window[2] * window[3] * 64 * (1 if subsampling == GRAY else hmax * vmax + 2)
 
 
-def entropy_decode(data, window=None):
+def packed_bound(blocks):
+    """The worst-case bytes of ``blocks`` blocks in the packed form (``fv_jpeg_packed_bound``)."""
+    return int(L.host_lib().fv_jpeg_packed_bound(ctypes.c_longlong(int(blocks))))
+
+
+def _aligned_bytes(n, align=16):
+    """A uint8 array of ``n`` bytes whose first byte is ``align``-byte aligned."""
+    raw = np.zeros(n + align, np.uint8)
+    lead = -raw.ctypes.data % align
+    return raw[lead:lead + n]
+
+
+def _decode_packed(data, win, out, rec):
+    return L.host_lib().fv_jpeg_entropy_decode_packed(ctypes.c_char_p(data), ctypes.c_longlong(len(data)), (ctypes.c_int * 4)(*win),
+                                                      ctypes.c_void_p(out.ctypes.data), ctypes.c_longlong(out.size),
+                                                      ctypes.c_void_p(rec.ctypes.data))
+
+
+def _rec_i64(rec, at):
+    u = rec.view(np.uint32)
+    return int(u[at]) | int(u[at + 1]) << 32
+
+
+def _rec_add(rec, at, delta):
+    u = rec.view(np.uint32)
+    v = _rec_i64(rec, at) + delta
+    u[at], u[at + 1] = v & 0xffffffff, v >> 32
+
+
+def unpack(record, packed):
+    """The packed form restated in numpy: the dense int16 coefficients (64 per block, natural order, the blocks numbered as
+    the dense form numbers them) of the packed ``record`` and the uint8 bytes it describes -- ``packed[0]`` is the byte
+    the record's offsets count from.  Raises ``ValueError`` where a header or a value lies outside ``packed``."""
+    record, packed = np.asarray(record, np.int32), np.ascontiguousarray(packed, np.uint8)
+    if record[0] != 2:
+        raise ValueError("unpack: not the record of a packed job")
+    blocks, hb, vb = int(record[17]), _rec_i64(record, 25), _rec_i64(record, 27)
+    if hb < 0 or hb % 16 or hb + 16 * blocks > packed.size or vb < 0 or vb % 2 or vb > packed.size:
+        raise ValueError("unpack: the headers do not lie inside the bytes")
+    hdr = packed[hb:hb + 16 * blocks].view("<u4").reshape(blocks, 4)
+    dense = np.zeros((blocks, 64), np.int16)
+    dense[:, 0] = (hdr[:, 3] & 0xffff).astype(np.uint16).view(np.int16)
+    for b in range(blocks):
+        mask = (int(hdr[b, 0]) | int(hdr[b, 1]) << 32) & ~1
+        ks = [k for k in range(64) if mask >> k & 1]
+        wide, off = int(hdr[b, 2]) >> 31, vb + (int(hdr[b, 2]) & 0x7fffffff)
+        if off % 2 or off + len(ks) * (1 + wide) > packed.size:
+            raise ValueError(f"unpack: the values of block {b} do not lie inside the bytes")
+        dense[b, ks] = packed[off:off + len(ks) * (1 + wide)].view("<i2" if wide else np.int8)
+    return dense.reshape(-1)
+
+
+def entropy_decode(data, window=None, packed=False):
     """The host decoder on its own (no GPU): ``(record, coefficients)`` -- the int32 record of ``FV_JPEG_REC_INTS`` words
-    and the int16 coefficients of ``window`` (default: the whole image), as include/fastvim_hip.h lays them out.  Raises
+    and the int16 coefficients of ``window`` (default: the whole image), as include/fastvim_hip.h lays them out.  With
+    ``packed=True``: ``(record, bytes)`` of the packed form, the uint8 bytes written (headers, then values).  Raises
     ``ValueError`` with the decoder's reason."""
     data = _as_bytes(data)
     h, w, _, cls, ok, reason, mx, my = _probe(data)
     if not ok:
         raise ValueError(f"fv_jpeg_entropy_decode: unserved file ({REASONS[reason]})")
     win = (0, 0, mx, my) if window is None else tuple(int(v) for v in window)
+    if packed:
+        out = _aligned_bytes(packed_bound(max(window_elements(cls, win), 0) // 64))
+        rec = np.zeros(REC_INTS, np.int32)
+        rc = _decode_packed(data, win, out, rec)
+        if rc != 0:
+            raise ValueError(f"fv_jpeg_entropy_decode_packed: {ERRORS.get(rc, 'error')} (code {rc})")
+        return rec, out[:_rec_i64(rec, 15)].copy()
     coef = np.zeros(max(window_elements(cls, win), 0), np.int16)
     rec = np.zeros(REC_INTS, np.int32)
     rc = L.host_lib().fv_jpeg_entropy_decode(ctypes.c_char_p(data), ctypes.c_longlong(len(data)), (ctypes.c_int * 4)(*win),
@@ -117,33 +180,58 @@ class JpegImageStage(ImageStage):
     ``put`` and ``put_jpeg`` may be mixed within a batch; a sample put as a decoded array has a zero-length JPEG job.
     ``commit()`` also copies the used part of the coefficient pool and the table; ``resample(out)`` runs ``fv_jpeg_idct``
     and ``fv_jpeg_rgb`` (``decode()``) in front of the two resample launches.  Their grids depend on the capacities only,
-    so with ``slots=1`` a captured ``resample`` replays correctly after a ``commit()`` of any other batch."""
+    so with ``slots=1`` a captured ``resample`` replays correctly after a ``commit()`` of any other batch.
 
-    def __init__(self, batch, out_size, capacity_bytes, coef_capacity_bytes, slots=2, device=None):
+    ``coef_format="packed"`` (default ``"dense"``) stages the packed form: ``coef_capacity_bytes`` then bounds the packed
+    pool of a slot, and ``plane_capacity_bytes`` the plane workspace, 64 bytes per block, which the packed pool no longer
+    implies (default ``4 * coef_capacity_bytes``: enough while a block packs to 16 bytes or more, and a header alone is
+    16).  A sample's packed size is known only after it is decoded: ``put_jpeg`` decodes into a scratch buffer of the
+    calling thread, reserves the exact size under the lock and copies into the pinned pool outside it, so the pool's
+    layout follows the order in which threads finish -- the pixels do not.  ``decode()`` runs ``fv_jpeg_idct_packed``."""
+
+    def __init__(self, batch, out_size, capacity_bytes, coef_capacity_bytes, slots=2, device=None, coef_format="dense",
+                 plane_capacity_bytes=None):
+        if coef_format not in ("dense", "packed"):
+            raise ValueError(f"JpegImageStage: coef_format {coef_format!r} is neither 'dense' nor 'packed'")
         super().__init__(batch, out_size, capacity_bytes, slots=slots, device=device)
-        self.coef_elems = (int(coef_capacity_bytes) + 127) // 128 * 64
+        self.coef_format = coef_format
+        self._lock = threading.RLock()
+        self.last_jpeg_fallbacks = 0
+        self.staged_coef_bytes = 0             # coefficient bytes of the batch committed last (packed: the pool bytes used)
+        self.staged_pool_bytes = 0             # of ``staged_bytes`` (pool bytes in use), those the host filled and sent
         n = int(L.lib().fv_jpeg_table_ints(L.i32(self.batch)))
         assert n == self.batch * REC_INTS + 2 * (self.batch + 1)
         for s in self._slots:
-            s.coef_pin = torch.zeros(self.coef_elems, dtype=torch.int16).pin_memory()
             s.table_pin = torch.zeros(n, dtype=torch.int32).pin_memory()
             s.table_np = s.table_pin.numpy()
             s.records = s.table_np[:self.batch * REC_INTS].reshape(self.batch, REC_INTS)
-            s.coef = torch.zeros(self.coef_elems, dtype=torch.int16, device=self.device)
             s.table = torch.zeros(n, dtype=torch.int32, device=self.device)
-            s.jused, s.jfallbacks = 0, 0
+            s.jused, s.pused, s.jfallbacks = 0, 0, 0
+        if coef_format == "packed":
+            self.coef_bytes = (int(coef_capacity_bytes) + 15) // 16 * 16
+            planes = 4 * self.coef_bytes if plane_capacity_bytes is None else int(plane_capacity_bytes)
+            self.plane_bytes = (planes + 63) // 64 * 64
+            for s in self._slots:
+                s.coef_pin = torch.zeros(self.coef_bytes, dtype=torch.uint8).pin_memory()
+                s.coef = torch.zeros(self.coef_bytes, dtype=torch.uint8, device=self.device)
+            self._planes = torch.zeros(self.plane_bytes, dtype=torch.uint8, device=self.device)
+            self._scratch = threading.local()
+            return
+        if plane_capacity_bytes is not None:
+            raise ValueError("JpegImageStage: plane_capacity_bytes belongs to coef_format='packed' (the dense form's plane "
+                             "workspace has the size of its coefficient pool)")
+        self.coef_elems = (int(coef_capacity_bytes) + 127) // 128 * 64
+        for s in self._slots:
+            s.coef_pin = torch.zeros(self.coef_elems, dtype=torch.int16).pin_memory()
+            s.coef = torch.zeros(self.coef_elems, dtype=torch.int16, device=self.device)
         self._planes = torch.zeros(self.coef_elems, dtype=torch.uint8, device=self.device)
-        self._lock = threading.RLock()
-        self.last_jpeg_fallbacks = 0
-        self.staged_coef_bytes = 0             # coefficient bytes of the batch committed last
-        self.staged_pool_bytes = 0             # of ``staged_bytes`` (pool bytes in use), those the host filled and sent
 
     def _filling(self):
         fresh = not self._open
         s = super()._filling()
         if fresh:
             s.records[:, 0] = 0                # no JPEG job anywhere
-            s.jused, s.jfallbacks = 0, 0
+            s.jused, s.pused, s.jfallbacks = 0, 0, 0
         return s
 
     def put(self, i, array_hwc_u8, crop=None, out_full=None, window=(0, 0), flip=False):
@@ -164,7 +252,9 @@ class JpegImageStage(ImageStage):
         """Stage sample ``i`` from the bytes of a JPEG file: the same meaning as ``put`` of the decoded image.  Reserves the
         crop's region of the pixel pool, writes the ordinary plan row and entropy-decodes the MCUs the crop needs into the
         pinned coefficient pool.  The decode is one ctypes call, and ctypes releases the GIL for its length: loader
-        threads that call ``put_jpeg`` for different samples decode in parallel (the reservations are under a lock)."""
+        threads that call ``put_jpeg`` for different samples decode in parallel (the reservations are under a lock).
+        With ``coef_format="packed"`` the decode comes first, into a scratch buffer of the thread, and the reservation of the
+        exact packed size after it (``_put_packed``)."""
         i, data = int(i), _as_bytes(data)
         H, W, _, cls, ok, _, _, _ = _probe(data)
         if not ok:
@@ -181,6 +271,8 @@ class JpegImageStage(ImageStage):
             return self._put_decoded(i, data, crop, out_full, window, flip)      # ``put`` resizes it with PIL on the host
         mcus = mcu_window(H, W, cls, (t, l, h, w))
         n = window_elements(cls, mcus)
+        if self.coef_format == "packed":
+            return self._put_packed(i, data, cls, mcus, n // 64, (t, l, h, w), (o_h, o_w), (win_y, win_x), flip)
         with self._lock:
             s = self._filling()
             if not 0 <= i < self.batch:
@@ -216,11 +308,51 @@ class JpegImageStage(ImageStage):
         rec[19:23] = (t, l, h, w)
         u[23], u[24] = off & 0xffffffff, off >> 32
 
+    def _put_packed(self, i, data, cls, mcus, blocks, crop, out_full, window, flip):
+        """``put_jpeg`` of the packed form: decode into this thread's scratch, reserve the exact size, copy."""
+        bound = 142 * blocks                                           # fv_jpeg_packed_bound
+        tl = self._scratch
+        if getattr(tl, "size", -1) < bound:
+            tl.buf = _aligned_bytes(max(bound, 1 << 16))
+            tl.size, tl.ptr = tl.buf.size, ctypes.c_void_p(tl.buf.ctypes.data)
+            tl.rec = np.zeros(REC_INTS, np.int32)
+            tl.rec_ptr = ctypes.c_void_p(tl.rec.ctypes.data)
+        rec = tl.rec
+        rc = L.host_lib().fv_jpeg_entropy_decode_packed(ctypes.c_char_p(data), ctypes.c_longlong(len(data)), (ctypes.c_int * 4)(*mcus),
+                                                        tl.ptr, ctypes.c_longlong(bound), tl.rec_ptr)
+        if rc != 0:
+            return self._put_decoded(i, data, crop, out_full, window, flip)      # a file the decoder gives up on
+        t, l, h, w = crop
+        nbytes, planes = _rec_i64(rec, 15), 64 * blocks
+        with self._lock:
+            s = self._filling()
+            if not 0 <= i < self.batch:
+                raise IndexError(f"ImageStage.put: sample {i} of a batch of {self.batch}")
+            if s.host.filled[i]:
+                raise ValueError(f"ImageStage.put: sample {i} was already put in this batch")
+            if s.jused + nbytes > self.coef_bytes:
+                raise ValueError(f"JpegImageStage.put_jpeg: sample {i} ({nbytes} packed coefficient bytes at offset {s.jused}) "
+                                 f"overflows coef_capacity_bytes = {self.coef_bytes}")
+            if s.pused + planes > self.plane_bytes:
+                raise ValueError(f"JpegImageStage.put_jpeg: sample {i} ({planes} plane bytes at offset {s.pused}) overflows "
+                                 f"plane_capacity_bytes = {self.plane_bytes}")
+            off = s.host.reserve(i, h, w, out_full[0], out_full[1], window[0], window[1], flip)
+            base, pbase = s.jused, s.pused
+            s.jused, s.pused = (base + nbytes + 15) // 16 * 16, pbase + planes
+        ctypes.memmove(s.coef_pin.data_ptr() + base, tl.ptr, nbytes)       # a foreign call: the GIL is released
+        for c in range(1 if cls == GRAY else 3):                   # offsets relative to the sample -> to the workspaces
+            _rec_add(rec, 9 + 2 * c, pbase)
+        _rec_add(rec, 25, base)
+        _rec_add(rec, 27, base)
+        rec[19:23] = crop
+        rec.view(np.uint32)[23:25] = (off & 0xffffffff, off >> 32)
+        s.records[i] = rec
+
     def _copy_pool(self, s):
         """Only the regions the HOST filled cross the link (samples put as arrays, fallbacks); a JPEG job's region is
         written by ``fv_jpeg_rgb``.  Neighbouring host regions go as one copy -- what lies between them is overwritten by
         the launches anyway."""
-        host = np.flatnonzero(s.records[:, 0] != 1)
+        host = np.flatnonzero(s.records[:, 0] == 0)
         spans = sorted((s.host.offset(i), int(s.host.plan[i, 2]) * int(s.host.plan[i, 3]) * 3) for i in host)
         runs = []
         for off, n in spans:
@@ -237,7 +369,7 @@ class JpegImageStage(ImageStage):
             s = self._filling()
             s.host.check_complete()
             r = s.records
-            job = r[:, 0] == 1
+            job = r[:, 0] != 0
             blocks = np.where(job, r[:, 17], 0).astype(np.int64)
             quads = np.where(job, (r[:, 21].astype(np.int64) * r[:, 22] + 3) // 4, 0)
             pre = np.zeros((2, self.batch + 1), np.int64)
@@ -249,18 +381,23 @@ class JpegImageStage(ImageStage):
             s.coef[:s.jused].copy_(s.coef_pin[:s.jused], non_blocking=True)
             s.table.copy_(s.table_pin, non_blocking=True)
             self.last_jpeg_fallbacks = s.jfallbacks
-            self.staged_coef_bytes = 2 * s.jused
+            self.staged_coef_bytes = s.jused if self.coef_format == "packed" else 2 * s.jused
             super().commit()
 
     def decode(self):
-        """The two JPEG launches on the slot committed last: coefficients -> sample planes (``fv_jpeg_idct``), planes ->
-        RGB crops in the pixel pool (``fv_jpeg_rgb``)."""
+        """The two JPEG launches on the slot committed last: coefficients -> sample planes (``fv_jpeg_idct``, or
+        ``fv_jpeg_idct_packed`` on the packed form), planes -> RGB crops in the pixel pool (``fv_jpeg_rgb``)."""
         s = self._ready
         if s is None:
             raise RuntimeError("JpegImageStage.decode: nothing was committed")
-        lib, st = L.lib(), L.stream_of(s.pool)
-        ne, b = ctypes.c_longlong(self.coef_elems), L.i32(self.batch)
-        L.check(lib.fv_jpeg_idct(L.ptr(s.coef), ne, L.ptr(s.table), L.ptr(self._planes), ne, b, st), "fv_jpeg_idct")
+        lib, st, b = L.lib(), L.stream_of(s.pool), L.i32(self.batch)
+        if self.coef_format == "packed":
+            ne = ctypes.c_longlong(self.plane_bytes)
+            L.check(lib.fv_jpeg_idct_packed(L.ptr(s.coef), ctypes.c_longlong(self.coef_bytes), L.ptr(s.table), L.ptr(self._planes),
+                                            ne, b, st), "fv_jpeg_idct_packed")
+        else:
+            ne = ctypes.c_longlong(self.coef_elems)
+            L.check(lib.fv_jpeg_idct(L.ptr(s.coef), ne, L.ptr(s.table), L.ptr(self._planes), ne, b, st), "fv_jpeg_idct")
         L.check(lib.fv_jpeg_rgb(L.ptr(self._planes), ne, L.ptr(s.table), L.ptr(s.pool), ctypes.c_longlong(self.capacity), b, st),
                 "fv_jpeg_rgb")
         self._record(s)

@@ -88,7 +88,10 @@ const char* fv_last_error(void);
  *      point changed.
  *      Later, still 3: fv_mae_noise and fv_mae_mask_plan_keyed were ADDED (the MAE masking noise as a function of a key
  *      block in device memory, and the masking plan of that noise without the noise tensor); fv_mae_mask_plan is
- *      unchanged. */
+ *      unchanged.
+ *      Later, still 3: fv_jpeg_entropy_decode_packed, fv_jpeg_packed_bound and fv_jpeg_idct_packed were ADDED (the packed
+ *      coefficient form: a mask and the non-zero values per block); fv_jpeg_rgb also reads records of packed jobs; no
+ *      signature changed. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -1226,6 +1229,43 @@ int fv_randaug_apply(const void* in, void* out, const int* plan, const void* ws,
  *   pool (HWC, pitch 3 w).  A crop's region must start 4-byte aligned in a 4-byte aligned pool.
  * For coefficient values no encoder writes the pixel values are unspecified (32-bit wrap-around, not libjpeg's 64-bit
  * intermediates and masked range table); memory safety holds regardless.
+ *
+ * THE PACKED FORM (opt-in; the dense form above stays the default).  A block of a photograph is mostly zeros, and the
+ * dense form sends all 64 coefficients of it over the link.  The packed form sends a 64-bit mask and the non-zero values.
+ * A sample's blocks are numbered as the dense form numbers them: component after component, each row-major over its
+ * (block rows, block columns) of the MCU window.  Per sample ONE contiguous piece of the coefficient pool holds
+ *   headers  `blocks` headers of 16 bytes, the first 16-byte aligned; a header is four little-endian uint32 words:
+ *              w0, w1   low and high word of a 64-bit mask: bit k (NATURAL order, k = 8 * row + column) is set exactly when
+ *                       AC coefficient k is non-zero; bit 0 is always clear
+ *              w2       bits 0..30: byte offset of the block's values relative to the sample's VALUE BASE, even;
+ *                       bit 31 `wide`: set exactly when some AC value of the block lies outside -128 .. 127
+ *              w3       low 16 bits: the DC coefficient as int16; high 16 bits 0
+ *   values   directly behind the headers (value base = first header + 16 * blocks): per block its non-zero AC
+ *            coefficients in ascending natural index, int8 each when `wide` is clear, little-endian int16 each when it is
+ *            set.  Every block's values start at an even offset: a block with an odd number of value bytes is followed by
+ *            one pad byte of 0 (so the bytes written are even).  A block with mask 0 has no values (its offset is where
+ *            the next block's values start).
+ * It is shaped for 8 lanes per block, lane r owning natural row r: lane r's coefficients are the set bits of mask byte r,
+ * its first value is number popcount(mask & ((1 << 8 r) - 1)) of the block.  No zigzag table on the device, no scatter; a
+ * DC-only block is mask == 0, known before any value is loaded.
+ * fv_jpeg_packed_bound(blocks): the worst case of a sample, blocks * (16 + 126) bytes (0 for blocks < 0).
+ * fv_jpeg_entropy_decode_packed(data, nbytes, window, out, out_capacity_bytes, record): parsing, window, early stop and
+ *   error codes of fv_jpeg_entropy_decode; writes the headers at `out` (16-byte aligned, else FV_ERR_INVALID) and the
+ *   values from out + 16 * blocks.  The capacity is checked as it goes: FV_JPEG_E_CAPACITY without a write at or beyond
+ *   out + out_capacity_bytes.  On an error there is no partial result.  The record differs from the dense one in
+ *     [0]        2: a packed JPEG job
+ *     [9..14]    per component the byte offset of its PLANE, low and high: 64 x the blocks in front of it; the caller adds
+ *                the sample's base in the plane workspace (a multiple of 8)
+ *     [15] [16]  BYTES written, low and high
+ *     [25] [26]  byte offset of the first header, [27] [28] of the value base, low and high -- relative to `out`; the
+ *                caller adds the offset of `out` in the pool (a multiple of 16)
+ *   and in nothing else (blocks, MCUs decoded and the quantisation tables included).
+ * fv_jpeg_idct_packed(pool, pool_bytes, table, planes, plane_bytes, batch, stream): fv_jpeg_idct on records with [0] == 2
+ *   (others are skipped, as fv_jpeg_idct skips these): same table, same contiguous share of blocks per workgroup, a grid
+ *   from min(pool_bytes / 16, plane_bytes / 64) alone, the same planes bit for bit.  Every header and value access is
+ *   checked against `pool_bytes` (values against its whole 4-byte words: they are read as aligned words) and every plane
+ *   store against `plane_bytes`; a record or a block that does not fit is skipped.  No atomics.  `pool` 16-byte aligned, `planes` 8.  fv_jpeg_rgb reads planes only and takes the records of
+ *   either form.
  * ---------------------------------------------------------------------- */
 #define FV_JPEG_INFO_INTS 8
 #define FV_JPEG_REC_INTS 224
@@ -1259,6 +1299,11 @@ int fv_jpeg_idct(const void* coef, long long coef_elems, const int* table, void*
                  fv_stream_t stream);
 int fv_jpeg_rgb(const void* planes, long long plane_bytes, const int* table, void* pool, long long pool_bytes, int batch,
                 fv_stream_t stream);
+long long fv_jpeg_packed_bound(long long blocks);
+int fv_jpeg_entropy_decode_packed(const void* data, long long nbytes, const int* window, void* out,
+                                  long long out_capacity_bytes, int* record);
+int fv_jpeg_idct_packed(const void* pool, long long pool_bytes, const int* table, void* planes, long long plane_bytes,
+                        int batch, fv_stream_t stream);
 
 #ifdef __cplusplus
 }
