@@ -47,6 +47,7 @@ C_ABI_SYMBOLS = (
     "fv_jpeg_probe", "fv_jpeg_entropy_decode", "fv_jpeg_table_ints", "fv_jpeg_idct", "fv_jpeg_rgb",
     "fv_jpeg_packed_bound", "fv_jpeg_entropy_decode_packed", "fv_jpeg_idct_packed",
     "fv_mae_noise", "fv_mae_mask_plan_keyed",
+    "fv_jpeg_index_bound", "fv_jpeg_build_index", "fv_jpeg_index_stage", "fv_jpeg_stream_table_ints", "fv_jpeg_huff",
 )
 
 
@@ -99,6 +100,9 @@ def lib():
         cdll.fv_randaug_workspace_bytes.restype = ctypes.c_longlong
         cdll.fv_jpeg_table_ints.restype = ctypes.c_longlong
         cdll.fv_jpeg_packed_bound.restype = ctypes.c_longlong
+        cdll.fv_jpeg_index_bound.restype = ctypes.c_longlong
+        cdll.fv_jpeg_build_index.restype = ctypes.c_longlong
+        cdll.fv_jpeg_stream_table_ints.restype = ctypes.c_longlong
         _lib = _DeviceGuarded(cdll)
     return _lib
 

@@ -18,7 +18,14 @@
 //   jpeg_rgb_kernel   a thread per QUAD of four consecutive pixels of a crop (12 bytes: three aligned 4-byte stores).
 // Both split the table's prefix sums into one contiguous share per workgroup: the grid depends on capacities only, so a
 // captured launch serves whatever batch the table describes when it runs.
+//
+//   jpeg_huff_kernel  the indexed path (include/fastvim_hip.h at THE INDEX), in front of jpeg_idct_kernel: a LANE per group
+//                     of S MCUs, decoded from its index entry by jpeg_huff_core.h.  Serial, divergent work with dependent
+//                     byte loads: one-wave workgroups spread the lanes over as many SIMDs as the batch has waves, and
+//                     neighbouring lanes decode neighbouring groups of one MCU row -- the nearest thing to equal work.
+//                     The Huffman tables are read from the stream pool through the caches.
 #include "common.h"
+#include "jpeg_huff_core.h"
 
 namespace {
 
@@ -327,6 +334,27 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_rgb_kernel(const uint8_t* __r
   }
 }
 
+constexpr int HUFF_THREADS = 64;
+constexpr int SREC = FV_JPEG_STREAM_REC_INTS;
+static_assert(fvhuff::ST_CODE == FV_JPEG_ST_CODE && fvhuff::ST_RUN == FV_JPEG_ST_RUN && fvhuff::ST_CAPACITY == FV_JPEG_ST_CAPACITY &&
+              fvhuff::ST_RECORD == FV_JPEG_ST_RECORD && fvhuff::SREC_INTS == SREC && fvhuff::MAX_MCUS == JP_MAX_MCUS,
+              "the core and the header agree");
+
+__global__ __launch_bounds__(HUFF_THREADS) void jpeg_huff_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
+                                                                  int* __restrict__ stable, int16_t* __restrict__ coef,
+                                                                  long long coef_elems, int batch) {
+  const int* pre = stable + (long long)batch * SREC;
+  const long long total = pre[batch];
+  const long long step = (long long)gridDim.x * HUFF_THREADS;
+  for (long long g = (long long)blockIdx.x * HUFF_THREADS + threadIdx.x; g < total; g += step) {
+    const int s = find_sample(pre, batch, g);
+    int* r = stable + (long long)s * SREC;
+    if (r[0] != 1) continue;                                    // the prefix sums give such a record no lane
+    const int st = fvhuff::run_lane(pool, pool_bytes, r, g - pre[s], coef, coef_elems);
+    if (st != fvhuff::ST_OK) r[fvhuff::SREC_STATUS] = st;       // a plain store; lanes that give up may race for it
+  }
+}
+
 bool batch_ok(int batch) { return batch >= 1 && batch <= 4096; }
 
 // grid of a launch over at most `units` work items, `per` per workgroup pass: from capacities only
@@ -380,6 +408,27 @@ extern "C" int fv_jpeg_rgb(const void* planes, long long plane_bytes, const int*
   FV_CHECK(((uintptr_t)table & 3) == 0 && ((uintptr_t)pool & 3) == 0, "jpeg_rgb: misaligned buffer");
   hipLaunchKernelGGL(jpeg_rgb_kernel, dim3(stride_grid(pool_bytes / 12 + batch, JP_THREADS)), dim3(JP_THREADS), 0,
                      (hipStream_t)stream, (const uint8_t*)planes, plane_bytes, table, (uint8_t*)pool, pool_bytes, batch);
+  FV_LAUNCH_CHECK();
+  return FV_OK;
+}
+
+extern "C" long long fv_jpeg_stream_table_ints(int batch) {
+  return batch_ok(batch) ? (long long)batch * FV_JPEG_STREAM_REC_INTS + (long long)batch + 1 : 0;
+}
+
+extern "C" int fv_jpeg_huff(const void* stream_pool, long long stream_bytes, int* stream_table, void* coef, long long coef_elems,
+                            int batch, fv_stream_t stream) {
+  FV_CHECK(stream_pool && stream_table && coef, "jpeg_huff: null pointer");
+  FV_CHECK(batch_ok(batch), "jpeg_huff: batch %d outside [1, 4096]", batch);
+  FV_CHECK(stream_bytes >= 0 && coef_elems >= 0, "jpeg_huff: negative capacity");
+  FV_CHECK(((uintptr_t)stream_pool & 15) == 0 && ((uintptr_t)stream_table & 3) == 0 && ((uintptr_t)coef & 15) == 0,
+           "jpeg_huff: misaligned buffer (stream pool and coefficients 16 bytes, table 4)");
+  // a lane takes a 16-byte entry at the least; one-wave workgroups, at most 32 per CU
+  long long need = (stream_bytes / 16 + HUFF_THREADS - 1) / HUFF_THREADS;
+  const long long cap = (long long)fv_cu_count() * 32;
+  if (need > cap) need = cap;
+  hipLaunchKernelGGL(jpeg_huff_kernel, dim3(need < 1 ? 1 : (int)need), dim3(HUFF_THREADS), 0, (hipStream_t)stream,
+                     (const uint8_t*)stream_pool, stream_bytes, stream_table, (int16_t*)coef, coef_elems, batch);
   FV_LAUNCH_CHECK();
   return FV_OK;
 }

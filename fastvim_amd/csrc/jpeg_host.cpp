@@ -1,7 +1,7 @@
 // The host half of the JPEG decode (include/fastvim_hip.h at fv_jpeg_probe): marker parser and Huffman decoder of baseline
 // JPEG files, plain C++ with nothing from HIP -- the file also compiles on its own with the host compiler
-// (tools/jpeg_host_check.cpp and tools/jpeg_packed_check.cpp run it under the address and undefined-behaviour
-// sanitizers).  No shared state -- the packed entry point keeps a scratch buffer per thread: any number of loader threads
+// (tools/jpeg_host_check.cpp, tools/jpeg_packed_check.cpp and tools/jpeg_index_check.cpp run it under the address and
+// undefined-behaviour sanitizers).  No shared state -- the packed entry point keeps a scratch buffer per thread: any number of loader threads
 // may decode at once.  Every read is checked against [data, data + nbytes), every write against
 // coef_out[0 : coef_capacity]; an anomaly is an error code, never a partial result.
 //
@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include "../../include/fastvim_hip.h"
+#include "jpeg_huff_core.h"
 
 namespace {
 
@@ -483,5 +484,223 @@ extern "C" int fv_jpeg_entropy_decode_packed(const void* data, long long nbytes,
   put_i64(record, 15, cur);
   put_i64(record, 25, 0);
   put_i64(record, 27, vbase);
+  return FV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------- THE INDEX
+// include/fastvim_hip.h at THE INDEX.  The builder decodes every group with the core the device runs (jpeg_huff_core.h),
+// each from its own entry with a fresh reader -- an entry is by construction what a lane starts from -- and moves a
+// (byte, bit) cursor over the stuffed stream by the bits the group consumed.
+namespace {
+
+constexpr uint32_t IDX_MAGIC = FV_JPEG_INDEX_MAGIC;
+constexpr int IDX_HEAD_WORDS = FV_JPEG_REC_INTS;                                        // the tables sit where the record's do
+constexpr int IDX_TABLE_WORDS = fvhuff::TABLES * fvhuff::TABLE_WORDS;
+constexpr long long IDX_ENTRIES = 4ll * (IDX_HEAD_WORDS + IDX_TABLE_WORDS);             // byte offset of the first entry
+constexpr int IDX_MAX_S = 65536;
+static_assert(IDX_ENTRIES == FV_JPEG_INDEX_HEAD_BYTES && IDX_ENTRIES % 16 == 0, "the header's size");
+static_assert(FV_JPEG_STREAM_REC_INTS == 32, "the stream record");
+
+inline uint32_t rd32(const void* p, long long word) {
+  uint32_t v;
+  memcpy(&v, (const uint8_t*)p + 4 * word, 4);
+  return v;
+}
+
+uint64_t fnv1a(const uint8_t* d, long long n) {
+  uint64_t h = 0xcbf29ce484222325ull;
+  for (long long i = 0; i < n; ++i) h = (h ^ d[i]) * 0x100000001b3ull;
+  return h;
+}
+
+void pack_table(const Huff& h, uint32_t* t) {
+  memset(t, 0, sizeof(uint32_t) * fvhuff::TABLE_WORDS);
+  memcpy(t, h.look, sizeof(h.look));
+  t[fvhuff::T_MAXCODE] = (uint32_t)-1;
+  for (int l = 1; l <= 17; ++l) t[fvhuff::T_MAXCODE + l] = (uint32_t)h.maxcode[l];
+  for (int l = 1; l <= 16; ++l) t[fvhuff::T_VALOFF + l] = (uint32_t)h.valoff[l];
+  t[fvhuff::T_NVALS] = (uint32_t)h.nvals;
+  memcpy(t + fvhuff::T_VALS, h.vals, (size_t)h.nvals);
+}
+
+struct Index {
+  const uint8_t* p;
+  int H, W, cls, ncomp, mcus_x, mcus_y, S, gpr;
+  long long groups, scan;
+  void entry(long long g, uint32_t* e) const { memcpy(e, p + IDX_ENTRIES + 16 * g, 16); }
+};
+
+// the header of an index against the file's size; nothing of it is trusted
+int open_index(const void* index, long long index_bytes, long long nbytes, Index& ix) {
+  if (index_bytes < IDX_ENTRIES + 16) return FV_JPEG_E_INDEX_FORMAT;
+  ix.p = (const uint8_t*)index;
+  if (rd32(index, 0) != IDX_MAGIC || rd32(index, 1) != FV_JPEG_INDEX_VERSION) return FV_JPEG_E_INDEX_FORMAT;
+  const long long nb = (long long)(((uint64_t)rd32(index, 3) << 32) | rd32(index, 2));
+  if (nb != nbytes || nbytes > 0x7fffffff) return FV_JPEG_E_INDEX_FILE;
+  ix.H = (int)rd32(index, 6); ix.W = (int)rd32(index, 7); ix.cls = (int)rd32(index, 8); ix.ncomp = (int)rd32(index, 9);
+  ix.mcus_x = (int)rd32(index, 10); ix.mcus_y = (int)rd32(index, 11); ix.S = (int)rd32(index, 12); ix.gpr = (int)rd32(index, 13);
+  ix.groups = (long long)rd32(index, 14);
+  ix.scan = (long long)(((uint64_t)rd32(index, 17) << 32) | rd32(index, 16));
+  if (ix.cls < 0 || ix.cls > 3 || ix.ncomp != (ix.cls == FV_JPEG_GRAY ? 1 : 3)) return FV_JPEG_E_INDEX_FORMAT;
+  if (ix.H < 1 || ix.H > 65535 || ix.W < 1 || ix.W > 65535 || ix.S < 1 || ix.S > IDX_MAX_S) return FV_JPEG_E_INDEX_FORMAT;
+  const int hmax = (ix.cls == FV_JPEG_422 || ix.cls == FV_JPEG_420) ? 2 : 1, vmax = ix.cls == FV_JPEG_420 ? 2 : 1;
+  if (ix.mcus_x != (ix.W + 8 * hmax - 1) / (8 * hmax) || ix.mcus_y != (ix.H + 8 * vmax - 1) / (8 * vmax)) return FV_JPEG_E_INDEX_FORMAT;
+  if (ix.gpr != (ix.mcus_x + ix.S - 1) / ix.S || ix.groups != (long long)ix.gpr * ix.mcus_y) return FV_JPEG_E_INDEX_FORMAT;
+  if (index_bytes < IDX_ENTRIES + 16 * (ix.groups + 1)) return FV_JPEG_E_INDEX_FORMAT;
+  if (ix.scan < 0 || ix.scan > nbytes) return FV_JPEG_E_INDEX_FORMAT;
+  return FV_OK;
+}
+
+}  // namespace
+
+extern "C" long long fv_jpeg_index_bound(int mcus_x, int mcus_y, int segment_mcus) {
+  if (mcus_x < 1 || mcus_y < 1 || mcus_x > 8192 || mcus_y > 8192 || segment_mcus < 1 || segment_mcus > IDX_MAX_S) return 0;
+  return IDX_ENTRIES + 16 * ((long long)((mcus_x + segment_mcus - 1) / segment_mcus) * mcus_y + 1);
+}
+
+extern "C" long long fv_jpeg_build_index(const void* data, long long nbytes, int segment_mcus, void* out,
+                                         long long out_capacity_bytes) {
+  if (!data || !out || nbytes < 0 || out_capacity_bytes < 0 || segment_mcus < 1 || segment_mcus > IDX_MAX_S) return FV_ERR_INVALID;
+  Frame f;
+  const uint8_t* d = (const uint8_t*)data;
+  parse(d, nbytes, f);
+  int reason = f.reason;
+  if (reason == FV_JPEG_R_OK && f.ri) reason = FV_JPEG_R_RESTART;
+  if (reason == FV_JPEG_R_OK && f.ncomp == 3 && (f.td[1] != f.td[2] || f.ta[1] != f.ta[2])) reason = FV_JPEG_R_CHROMA_TABLES;
+  if (reason != FV_JPEG_R_OK) {
+    if (out_capacity_bytes >= 4) memcpy(out, &reason, 4);
+    return FV_JPEG_E_UNSERVED;
+  }
+  if (nbytes > 0x7fffffff) return FV_JPEG_E_CAPACITY;
+  const int S = segment_mcus, gpr = (f.mcus_x + S - 1) / S;
+  const long long groups = (long long)gpr * f.mcus_y, total = IDX_ENTRIES + 16 * (groups + 1);
+  if (total > out_capacity_bytes) return FV_JPEG_E_CAPACITY;
+  uint32_t head[IDX_HEAD_WORDS];
+  memset(head, 0, sizeof(head));
+  const uint64_t hash = fnv1a(d, nbytes);
+  head[0] = IDX_MAGIC; head[1] = FV_JPEG_INDEX_VERSION;
+  head[2] = (uint32_t)nbytes; head[3] = (uint32_t)((uint64_t)nbytes >> 32);
+  head[4] = (uint32_t)hash; head[5] = (uint32_t)(hash >> 32);
+  head[6] = (uint32_t)f.H; head[7] = (uint32_t)f.W; head[8] = (uint32_t)f.cls; head[9] = (uint32_t)f.ncomp;
+  head[10] = (uint32_t)f.mcus_x; head[11] = (uint32_t)f.mcus_y; head[12] = (uint32_t)S; head[13] = (uint32_t)gpr;
+  head[14] = (uint32_t)groups;
+  head[16] = (uint32_t)f.scan; head[17] = (uint32_t)((uint64_t)f.scan >> 32);
+  for (int c = 0; c < f.ncomp; ++c)
+    for (int k = 0; k < 64; ++k) head[32 + 64 * c + k] = f.qt[f.ctq[c]][k];
+  // the tables the walk below reads are the ones that go into the index
+  uint32_t* tables = (uint32_t*)malloc(sizeof(uint32_t) * IDX_TABLE_WORDS);
+  if (!tables) return FV_JPEG_E_CAPACITY;
+  const int cc = f.ncomp == 3 ? 1 : 0;
+  pack_table(f.huff[0][f.td[0]], tables);
+  pack_table(f.huff[0][f.td[cc]], tables + fvhuff::TABLE_WORDS);
+  pack_table(f.huff[1][f.ta[0]], tables + 2 * fvhuff::TABLE_WORDS);
+  pack_table(f.huff[1][f.ta[cc]], tables + 3 * fvhuff::TABLE_WORDS);
+  uint8_t* o = (uint8_t*)out;
+  memcpy(o, head, sizeof(head));
+  memcpy(o + sizeof(head), tables, sizeof(uint32_t) * IDX_TABLE_WORDS);
+  fvhuff::Place nowhere{f.cls, 0, 0, 0, 0, {0, 0, 0}};             // an empty window: every block is dropped
+  uint32_t byte = (uint32_t)f.scan, bit = 0;
+  int pred[3] = {0, 0, 0};
+  int rc = FV_OK;
+  long long g = 0;
+  for (int my = 0; my < f.mcus_y && rc == FV_OK; ++my)
+    for (int gx = 0; gx < gpr && rc == FV_OK; ++gx, ++g) {
+      const uint32_t e[4] = {byte, bit, (uint32_t)(uint16_t)pred[0] | (uint32_t)(uint16_t)pred[1] << 16, (uint32_t)(uint16_t)pred[2]};
+      memcpy(o + IDX_ENTRIES + 16 * g, e, 16);
+      const int count = f.mcus_x - gx * S < S ? f.mcus_x - gx * S : S;
+      fvhuff::Reader end;
+      const int st = fvhuff::decode_group(d, (uint32_t)nbytes, byte, (int)bit, pred[0], pred[1], pred[2], tables, nowhere, my,
+                                          gx * S, count, nullptr, 0, &end);
+      if (st != fvhuff::ST_OK) { rc = st == fvhuff::ST_RUN ? FV_JPEG_E_RUN : FV_JPEG_E_CODE; break; }
+      if (fvhuff::past_end(end)) { rc = FV_JPEG_E_TRUNCATED; break; }
+      // the cursor moves over whole stuffed bytes: it never rests on a stuffed 0x00
+      uint32_t left = fvhuff::consumed(end);
+      while (left >= 8) {
+        if ((long long)byte >= nbytes) { rc = FV_JPEG_E_TRUNCATED; break; }
+        byte += d[byte] == 0xFF ? 2 : 1;
+        left -= 8;
+      }
+      bit = left;
+    }
+  free(tables);
+  if (rc != FV_OK) return rc;
+  const uint32_t e[4] = {byte, bit, (uint32_t)(uint16_t)pred[0] | (uint32_t)(uint16_t)pred[1] << 16, (uint32_t)(uint16_t)pred[2]};
+  memcpy(o + IDX_ENTRIES + 16 * groups, e, 16);                   // the end sentinel
+  return total;
+}
+
+extern "C" int fv_jpeg_index_stage(const void* data, long long nbytes, const void* index, long long index_bytes,
+                                   const int* window, int verify, void* pool, long long pool_capacity_bytes,
+                                   long long* pool_used, long long coef_base, int* record, int* stream_record) {
+  if (!data || !index || !window || !pool || !pool_used || !record || !stream_record || nbytes < 0 || index_bytes < 0 ||
+      pool_capacity_bytes < 0 || *pool_used < 0 || coef_base < 0 || (coef_base & 7) || ((uintptr_t)pool & 15))
+    return FV_ERR_INVALID;
+  Index ix;
+  int rc = open_index(index, index_bytes, nbytes, ix);
+  if (rc != FV_OK) return rc;
+  const uint8_t* d = (const uint8_t*)data;
+  if (verify) {
+    const uint64_t hash = fnv1a(d, nbytes);
+    if (rd32(index, 4) != (uint32_t)hash || rd32(index, 5) != (uint32_t)(hash >> 32)) return FV_JPEG_E_INDEX_FILE;
+  }
+  Frame geo;                                                      // only what window_of reads
+  geo.ncomp = ix.ncomp; geo.mcus_x = ix.mcus_x; geo.mcus_y = ix.mcus_y;
+  geo.ch[0] = (ix.cls == FV_JPEG_422 || ix.cls == FV_JPEG_420) ? 2 : 1;
+  geo.cv[0] = ix.cls == FV_JPEG_420 ? 2 : 1;
+  Window w;
+  rc = window_of(geo, window, w);
+  if (rc != FV_OK) return rc;
+  const int gx0 = w.x0 / ix.S, gx1 = (w.x0 + w.mw - 1) / ix.S, gw = gx1 - gx0 + 1;
+  const long long lanes = (long long)gw * w.mh;
+  // every entry a lane starts from, and the one behind each row's last group, inside the scan and in file order
+  uint32_t e[4];
+  long long before = ix.scan * 8;
+  for (int y = w.y0; y < w.y0 + w.mh; ++y)
+    for (int gx = gx0; gx <= gx1 + 1; ++gx) {
+      ix.entry((long long)y * ix.gpr + gx, e);
+      const long long at = (long long)e[0] * 8 + e[1];
+      if (e[1] > 7 || (long long)e[0] > nbytes || at < before) return FV_JPEG_E_INDEX_ENTRY;
+      before = at;
+    }
+  ix.entry((long long)w.y0 * ix.gpr + gx0, e);
+  const long long first = e[0];
+  ix.entry((long long)(w.y0 + w.mh - 1) * ix.gpr + gx1 + 1, e);
+  // the byte the next group starts in belongs to this one up to its bit; a 0xFF there is read with its stuffed 0x00
+  const long long end = (long long)e[0] + 2 < nbytes ? (long long)e[0] + 2 : nbytes;
+  const long long len = end - first, len16 = (len + 15) / 16 * 16;
+  const long long base = (*pool_used + 15) / 16 * 16, tbytes = 4ll * IDX_TABLE_WORDS;
+  if (len < 0 || base + tbytes + 16 * lanes + len16 > pool_capacity_bytes) return FV_JPEG_E_CAPACITY;
+  uint8_t* o = (uint8_t*)pool + base;
+  memcpy(o, ix.p + 4 * IDX_HEAD_WORDS, (size_t)tbytes);
+  for (int y = 0; y < w.mh; ++y)
+    memcpy(o + tbytes + 16ll * y * gw, ix.p + IDX_ENTRIES + 16 * ((long long)(w.y0 + y) * ix.gpr + gx0), 16 * (size_t)gw);
+  memcpy(o + tbytes + 16 * lanes, d + first, (size_t)len);
+  memset(o + tbytes + 16 * lanes + len, 0, (size_t)(len16 - len));
+  *pool_used = base + tbytes + 16 * lanes + len16;
+
+  memset(record, 0, sizeof(int) * FV_JPEG_REC_INTS);
+  record[0] = 1;
+  record[1] = ix.H; record[2] = ix.W; record[3] = ix.ncomp; record[4] = ix.cls;
+  record[5] = w.x0; record[6] = w.y0; record[7] = w.mw; record[8] = w.mh;
+  memset(stream_record, 0, sizeof(int) * FV_JPEG_STREAM_REC_INTS);
+  for (int c = 0; c < ix.ncomp; ++c) {
+    put_i64(record, 9 + 2 * c, coef_base + w.first[c] * 64);
+    put_i64(stream_record, 10 + 2 * c, coef_base + w.first[c] * 64);
+  }
+  put_i64(record, 15, w.blocks * 64);
+  record[17] = (int)w.blocks;
+  record[18] = (int)((long long)(w.y0 + w.mh - 1) * ix.mcus_x + w.x0 + w.mw);
+  memcpy(record + 32, ix.p + 4 * 32, sizeof(int) * 192);
+  stream_record[0] = 1;
+  stream_record[1] = ix.cls;
+  stream_record[2] = w.x0; stream_record[3] = w.y0; stream_record[4] = w.mw; stream_record[5] = w.mh;
+  stream_record[6] = ix.mcus_x;
+  stream_record[7] = ix.S;
+  stream_record[8] = gx0; stream_record[9] = gw;
+  put_i64(stream_record, 16, base);
+  put_i64(stream_record, 18, base + tbytes);
+  put_i64(stream_record, 20, base + tbytes + 16 * lanes);
+  stream_record[22] = (int)len;
+  stream_record[23] = (int)first;
   return FV_OK;
 }

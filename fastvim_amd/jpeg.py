@@ -20,7 +20,16 @@ measured in DESIGN.md; ``unpack`` restates the format in numpy.
 Served: baseline (SOF0) 8-bit Huffman files with one interleaved scan; grayscale, or YCbCr at 4:4:4, 4:2:2 (2x1) or 4:2:0
 (2x2).  A file outside that (progressive, arithmetic, 12-bit, CMYK, RGB-coded, other sampling, several scans, 16-bit
 tables), and a file the entropy decoder returns an error for, is decoded by PIL on the host and staged as ``put`` stages
-it -- identical by construction; ``last_jpeg_fallbacks`` counts them."""
+it -- identical by construction; ``last_jpeg_fallbacks`` counts them.
+
+INDEXED FILES (opt-in): a file that is read every epoch can be decoded once into a sidecar index (``build_index``) that
+records, for every group of ``segment_mcus`` MCUs, where its bits start and what the DC predictors are there.  A stage
+built with ``stream_capacity_bytes`` then takes the FILE BYTES of the crop's groups (``put_jpeg_indexed``) and the device
+decodes the Huffman codes too, one lane per group (``fv_jpeg_huff``); the host only copies::
+
+    idx = jpeg.build_index(raw)                            # once per file, kept next to it
+    stage = JpegImageStage(B, 224, capacity_bytes=B << 20, coef_capacity_bytes=B << 21, stream_capacity_bytes=B << 17)
+    stage.put_jpeg_indexed(k, raw, idx, crop=(i, j, h, w), flip=f)"""
 import ctypes
 import io
 import threading
@@ -30,7 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .resample import ImageStage, _pair, resample_ok
+from .resample import ALIGN, ImageStage, _pair, resample_ok
 
 REC_INTS = 224            # FV_JPEG_REC_INTS
 INFO_INTS = 8             # FV_JPEG_INFO_INTS
@@ -40,6 +49,13 @@ REASONS = ("served", "progressive", "arithmetic coding", "not 8-bit precision", 
            "16-bit quantisation tables", "malformed or not a JPEG", "frame type other than SOF0")
 ERRORS = {-10: "unserved", -11: "data ends early", -12: "bad Huffman code", -13: "run past 63", -14: "wrong restart marker",
           -15: "coefficient capacity", -16: "window outside the image"}
+# the index (include/fastvim_hip.h at THE INDEX)
+INDEX_REASONS = REASONS + ("restart interval", "different Huffman tables for the two chroma components")
+INDEX_ERRORS = {-15: "capacity", -17: "not an index of this version, or an inconsistent header",
+                -18: "the index belongs to another file (size or hash)", -19: "an index entry outside the scan or out of order"}
+INDEX_MAGIC, INDEX_VERSION, INDEX_HEAD_BYTES = 0x58494A46, 1, 6592
+SREC_INTS = 32            # FV_JPEG_STREAM_REC_INTS
+DEFAULT_SEGMENT_MCUS = 1  # S: MCUs per group; the S of the lowest fv_jpeg_huff time in profiles/jpeg_index_bench.log
 _MCU = ((1, 1), (2, 1), (2, 2), (1, 1))  # (h_max, v_max) of a sampling class
 
 
@@ -167,6 +183,74 @@ def entropy_decode(data, window=None, packed=False):
     return rec, coef
 
 
+class JpegIndexInfo(NamedTuple):
+    nbytes: int           # of the file
+    hash: int             # FNV-1a 64 of its bytes
+    height: int
+    width: int
+    subsampling: int
+    components: int
+    mcus_x: int
+    mcus_y: int
+    segment_mcus: int     # S
+    groups_per_row: int
+    groups: int
+    scan: int             # offset of the first entropy-coded byte
+
+
+def build_index(raw, segment_mcus=DEFAULT_SEGMENT_MCUS):
+    """The index of a JPEG file as ``bytes`` (host code: no GPU needed, no state): per group of ``segment_mcus`` MCUs of
+    an MCU row the bit position and the DC predictors, with the tables the device decodes from.  Built once per file and
+    kept; ``put_jpeg_indexed`` takes it.  ``ValueError`` with the reason for a file that is not indexed (unserved files,
+    restart intervals): those keep ``put_jpeg``."""
+    raw, S = _as_bytes(raw), int(segment_mcus)
+    if not 1 <= S <= 65536:
+        raise ValueError(f"build_index: segment_mcus {S} outside [1, 65536]")
+    info = _probe(raw)
+    if not info[4]:
+        raise ValueError(f"build_index: unserved file ({REASONS[info[5]]})")
+    lib = L.host_lib()
+    bound = int(lib.fv_jpeg_index_bound(L.i32(info[6]), L.i32(info[7]), L.i32(S)))
+    out = np.zeros(max(bound, 16), np.uint8)
+    n = int(lib.fv_jpeg_build_index(ctypes.c_char_p(raw), ctypes.c_longlong(len(raw)), L.i32(S), ctypes.c_void_p(out.ctypes.data),
+                                    ctypes.c_longlong(out.size)))
+    if n == -10:
+        raise ValueError(f"build_index: file not indexed ({INDEX_REASONS[int(out[:4].view('<i4')[0])]})")
+    if n <= 0:
+        raise ValueError(f"build_index: {ERRORS.get(n, 'error')} (code {n})")
+    return out[:n].tobytes()
+
+
+def index_info(index):
+    """The fields of an index's header.  ``ValueError`` for bytes that are not an index of this version."""
+    index = _as_bytes(index)
+    if len(index) < INDEX_HEAD_BYTES + 16:
+        raise ValueError("index_info: too short for an index")
+    w = np.frombuffer(index, "<u4", 32)
+    if int(w[0]) != INDEX_MAGIC or int(w[1]) != INDEX_VERSION:
+        raise ValueError(f"index_info: magic {int(w[0]):#x} version {int(w[1])}: not an index of version {INDEX_VERSION}")
+    return JpegIndexInfo(int(w[2]) | int(w[3]) << 32, int(w[4]) | int(w[5]) << 32, int(w[6]), int(w[7]), int(w[8]), int(w[9]),
+                         int(w[10]), int(w[11]), int(w[12]), int(w[13]), int(w[14]), int(w[16]) | int(w[17]) << 32)
+
+
+def index_stage(raw, index, window=None, verify=False):
+    """The host half of the indexed path on its own (no GPU): ``(record, stream_record, pool)`` -- the dense record, the
+    stream record and the uint8 bytes ``fv_jpeg_index_stage`` appends to a stream pool for the MCU ``window`` (default: the
+    whole image; the record's offsets count from 0).  ``ValueError`` with the reason where the index does not fit the file."""
+    raw, index = _as_bytes(raw), _as_bytes(index)
+    ix = index_info(index)
+    win = (0, 0, ix.mcus_x, ix.mcus_y) if window is None else tuple(int(v) for v in window)
+    pool = _aligned_bytes(len(raw) + len(index) + 64)
+    rec, srec, used = np.zeros(REC_INTS, np.int32), np.zeros(SREC_INTS, np.int32), ctypes.c_longlong(0)
+    rc = L.host_lib().fv_jpeg_index_stage(ctypes.c_char_p(raw), ctypes.c_longlong(len(raw)), ctypes.c_char_p(index),
+                                          ctypes.c_longlong(len(index)), (ctypes.c_int * 4)(*win), L.i32(bool(verify)),
+                                          ctypes.c_void_p(pool.ctypes.data), ctypes.c_longlong(pool.size), ctypes.byref(used),
+                                          ctypes.c_longlong(0), ctypes.c_void_p(rec.ctypes.data), ctypes.c_void_p(srec.ctypes.data))
+    if rc != 0:
+        raise ValueError(f"fv_jpeg_index_stage: {INDEX_ERRORS.get(rc, ERRORS.get(rc, 'error'))} (code {rc})")
+    return rec, srec, pool[:used.value].copy()
+
+
 def _pil_decode(data):
     from PIL import Image
     return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
@@ -187,18 +271,35 @@ class JpegImageStage(ImageStage):
     implies (default ``4 * coef_capacity_bytes``: enough while a block packs to 16 bytes or more, and a header alone is
     16).  A sample's packed size is known only after it is decoded: ``put_jpeg`` decodes into a scratch buffer of the
     calling thread, reserves the exact size under the lock and copies into the pinned pool outside it, so the pool's
-    layout follows the order in which threads finish -- the pixels do not.  ``decode()`` runs ``fv_jpeg_idct_packed``."""
+    layout follows the order in which threads finish -- the pixels do not.  ``decode()`` runs ``fv_jpeg_idct_packed``.
+
+    ``stream_capacity_bytes`` (default 0: none of this exists) sets up the INDEXED path of the dense form: per slot a pinned
+    and a device STREAM POOL -- per indexed sample the four Huffman tables, the index entries of the groups its MCU window
+    meets and the file bytes of those groups -- the stream table and its status words.  ``put_jpeg_indexed`` fills them;
+    its coefficients never cross the link: their space is taken from the TOP of the coefficient pool downward, against
+    the same ``coef_capacity_bytes``, and ``fv_jpeg_huff`` writes them in front of ``fv_jpeg_idct``.  ``segment_capacity``
+    bounds the groups (lanes) of a batch; 0: only the stream pool bounds them, 16 bytes each."""
 
     def __init__(self, batch, out_size, capacity_bytes, coef_capacity_bytes, slots=2, device=None, coef_format="dense",
-                 plane_capacity_bytes=None):
+                 plane_capacity_bytes=None, stream_capacity_bytes=0, segment_capacity=0):
         if coef_format not in ("dense", "packed"):
             raise ValueError(f"JpegImageStage: coef_format {coef_format!r} is neither 'dense' nor 'packed'")
+        if int(stream_capacity_bytes) < 0 or int(segment_capacity) < 0:
+            raise ValueError("JpegImageStage: negative stream_capacity_bytes or segment_capacity")
+        if int(stream_capacity_bytes) and coef_format != "dense":
+            raise ValueError("JpegImageStage: the indexed path (stream_capacity_bytes) writes dense coefficients: "
+                             "coef_format='packed' is not accepted with it")
+        if int(segment_capacity) and not int(stream_capacity_bytes):
+            raise ValueError("JpegImageStage: segment_capacity belongs to the indexed path (stream_capacity_bytes)")
         super().__init__(batch, out_size, capacity_bytes, slots=slots, device=device)
         self.coef_format = coef_format
         self._lock = threading.RLock()
         self.last_jpeg_fallbacks = 0
         self.staged_coef_bytes = 0             # coefficient bytes of the batch committed last (packed: the pool bytes used)
         self.staged_pool_bytes = 0             # of ``staged_bytes`` (pool bytes in use), those the host filled and sent
+        self.stream_bytes = (int(stream_capacity_bytes) + 15) // 16 * 16
+        self.segment_capacity = int(segment_capacity)
+        self.staged_stream_bytes = 0           # stream pool bytes of the batch committed last: tables, entries, file bytes
         n = int(L.lib().fv_jpeg_table_ints(L.i32(self.batch)))
         assert n == self.batch * REC_INTS + 2 * (self.batch + 1)
         for s in self._slots:
@@ -207,6 +308,7 @@ class JpegImageStage(ImageStage):
             s.records = s.table_np[:self.batch * REC_INTS].reshape(self.batch, REC_INTS)
             s.table = torch.zeros(n, dtype=torch.int32, device=self.device)
             s.jused, s.pused, s.jfallbacks = 0, 0, 0
+            s.jtop, s.sused, s.lanes = 0, 0, 0
         if coef_format == "packed":
             self.coef_bytes = (int(coef_capacity_bytes) + 15) // 16 * 16
             planes = 4 * self.coef_bytes if plane_capacity_bytes is None else int(plane_capacity_bytes)
@@ -225,6 +327,16 @@ class JpegImageStage(ImageStage):
             s.coef_pin = torch.zeros(self.coef_elems, dtype=torch.int16).pin_memory()
             s.coef = torch.zeros(self.coef_elems, dtype=torch.int16, device=self.device)
         self._planes = torch.zeros(self.coef_elems, dtype=torch.uint8, device=self.device)
+        if self.stream_bytes:
+            m = int(L.lib().fv_jpeg_stream_table_ints(L.i32(self.batch)))
+            assert m == self.batch * SREC_INTS + self.batch + 1
+            for s in self._slots:
+                s.stream_pin = torch.zeros(self.stream_bytes, dtype=torch.uint8).pin_memory()
+                s.stream = torch.zeros(self.stream_bytes + 16, dtype=torch.uint8, device=self.device)      # a zero tail
+                s.stable_pin = torch.zeros(m, dtype=torch.int32).pin_memory()
+                s.stable_np = s.stable_pin.numpy()
+                s.srecords = s.stable_np[:self.batch * SREC_INTS].reshape(self.batch, SREC_INTS)
+                s.stable = torch.zeros(m, dtype=torch.int32, device=self.device)
 
     def _filling(self):
         fresh = not self._open
@@ -232,6 +344,9 @@ class JpegImageStage(ImageStage):
         if fresh:
             s.records[:, 0] = 0                # no JPEG job anywhere
             s.jused, s.pused, s.jfallbacks = 0, 0, 0
+            s.jtop, s.sused, s.lanes = getattr(self, "coef_elems", 0), 0, 0      # indexed samples reserve from the top down
+            if self.stream_bytes:
+                s.srecords[:] = 0
         return s
 
     def put(self, i, array_hwc_u8, crop=None, out_full=None, window=(0, 0), flip=False):
@@ -279,7 +394,7 @@ class JpegImageStage(ImageStage):
                 raise IndexError(f"ImageStage.put: sample {i} of a batch of {self.batch}")
             if s.host.filled[i]:
                 raise ValueError(f"ImageStage.put: sample {i} was already put in this batch")
-            if s.jused + n > self.coef_elems:
+            if s.jused + n > s.jtop:           # the capacity, less what indexed samples of the batch took from the top
                 raise ValueError(f"JpegImageStage.put_jpeg: sample {i} ({2 * n} coefficient bytes at offset {2 * s.jused}) "
                                  f"overflows coef_capacity_bytes = {2 * self.coef_elems}")
             off = s.host.reserve(i, h, w, o_h, o_w, win_y, win_x, flip)
@@ -307,6 +422,73 @@ class JpegImageStage(ImageStage):
             u[9 + 2 * c], u[10 + 2 * c] = e & 0xffffffff, e >> 32
         rec[19:23] = (t, l, h, w)
         u[23], u[24] = off & 0xffffffff, off >> 32
+
+    def put_jpeg_indexed(self, i, data, index, crop=None, out_full=None, window=(0, 0), flip=False, verify=False):
+        """``put_jpeg`` of a file whose index (``build_index``) is at hand: the same meaning, argument checks and PIL
+        fallback outside the resampler's range -- but no Huffman code is decoded here.  The index is checked against the
+        file (magic, version, size; with ``verify`` the hash of the bytes too; every entry used inside the scan and in
+        file order: ``ValueError`` otherwise), then the tables, the entries of the groups the crop's MCU window meets and the
+        file bytes of those groups are copied into the pinned stream pool (one foreign call), and the ordinary dense
+        record and the stream record are written.  The window's coefficient space is reserved from the top of the
+        coefficient pool; ``fv_jpeg_huff`` fills it on the device."""
+        if not self.stream_bytes:
+            raise RuntimeError("JpegImageStage.put_jpeg_indexed: the stage was built without stream_capacity_bytes")
+        i, data, index = int(i), _as_bytes(data), _as_bytes(index)
+        try:
+            ix = index_info(index)
+        except ValueError as e:
+            raise ValueError(f"JpegImageStage.put_jpeg_indexed: sample {i}: {e}") from None
+        if ix.nbytes != len(data):
+            raise ValueError(f"JpegImageStage.put_jpeg_indexed: sample {i}: the index is of a file of {ix.nbytes} bytes, not {len(data)}")
+        H, W, cls = ix.height, ix.width, ix.subsampling
+        if not (0 <= cls <= 3 and 1 <= H <= 65535 and 1 <= W <= 65535 and 1 <= ix.segment_mcus <= 65536):
+            raise ValueError(f"JpegImageStage.put_jpeg_indexed: sample {i}: {INDEX_ERRORS[-17]}")
+        t, l, h, w = (0, 0, H, W) if crop is None else (int(v) for v in crop)
+        if min(t, l) < 0 or h < 1 or w < 1 or t + h > H or l + w > W:
+            raise ValueError(f"ImageStage.put: crop {tuple(crop)} of sample {i} does not lie inside its {H}x{W} image")
+        o_h, o_w = (self.s_h, self.s_w) if out_full is None else _pair(out_full)
+        win_y, win_x = (int(v) for v in window)
+        if o_h < 1 or o_w < 1 or win_y < 0 or win_x < 0 or win_y + self.s_h > o_h or win_x + self.s_w > o_w:
+            raise ValueError(f"ImageStage.put: the {self.s_h}x{self.s_w} window at {(win_y, win_x)} of sample {i} does not lie "
+                             f"inside its {o_h}x{o_w} resize")
+        if not resample_ok(self.batch, self.s_h, self.s_w, h, w, o_h, o_w, win_y, win_x):
+            return self._put_decoded(i, data, crop, out_full, window, flip)      # ``put`` resizes it with PIL on the host
+        mcus = mcu_window(H, W, cls, (t, l, h, w))
+        n = window_elements(cls, mcus)
+        S = ix.segment_mcus
+        lanes = ((mcus[0] + mcus[2] - 1) // S - mcus[0] // S + 1) * mcus[3]
+        with self._lock:
+            s = self._filling()
+            if not 0 <= i < self.batch:
+                raise IndexError(f"ImageStage.put: sample {i} of a batch of {self.batch}")
+            if s.host.filled[i]:
+                raise ValueError(f"ImageStage.put: sample {i} was already put in this batch")
+            if s.jtop - n < s.jused:
+                raise ValueError(f"JpegImageStage.put_jpeg_indexed: sample {i} ({2 * n} coefficient bytes below offset {2 * s.jtop}) "
+                                 f"overflows coef_capacity_bytes = {2 * self.coef_elems}")
+            if self.segment_capacity and s.lanes + lanes > self.segment_capacity:
+                raise ValueError(f"JpegImageStage.put_jpeg_indexed: sample {i} ({lanes} groups after {s.lanes}) overflows "
+                                 f"segment_capacity = {self.segment_capacity}")
+            at = (s.host.used + ALIGN - 1) // ALIGN * ALIGN            # ``reserve``'s own check, before anything is written
+            if at + h * w * 3 > self.capacity:
+                raise ValueError(f"ImageStage.put: sample {i} ({h * w * 3} bytes at offset {at}) overflows capacity_bytes = "
+                                 f"{self.capacity}")
+            rec, srec, used = s.records[i], s.srecords[i], ctypes.c_longlong(s.sused)
+            rc = L.host_lib().fv_jpeg_index_stage(ctypes.c_char_p(data), ctypes.c_longlong(len(data)), ctypes.c_char_p(index),
+                                                  ctypes.c_longlong(len(index)), (ctypes.c_int * 4)(*mcus), L.i32(bool(verify)),
+                                                  ctypes.c_void_p(s.stream_pin.data_ptr()), ctypes.c_longlong(self.stream_bytes),
+                                                  ctypes.byref(used), ctypes.c_longlong(s.jtop - n),
+                                                  ctypes.c_void_p(rec.ctypes.data), ctypes.c_void_p(srec.ctypes.data))
+            if rc != 0:
+                rec[:] = 0
+                srec[:] = 0
+                what = "stream_capacity_bytes" if rc == -15 else "the index"
+                raise ValueError(f"JpegImageStage.put_jpeg_indexed: sample {i}: {INDEX_ERRORS.get(rc, ERRORS.get(rc, 'error'))} "
+                                 f"(code {rc}; {what})")
+            off = s.host.reserve(i, h, w, o_h, o_w, win_y, win_x, flip)
+            s.jtop, s.sused, s.lanes = s.jtop - n, used.value, s.lanes + lanes
+            rec[19:23] = (t, l, h, w)
+            rec.view(np.uint32)[23:25] = (off & 0xffffffff, off >> 32)
 
     def _put_packed(self, i, data, cls, mcus, blocks, crop, out_full, window, flip):
         """``put_jpeg`` of the packed form: decode into this thread's scratch, reserve the exact size, copy."""
@@ -380,6 +562,16 @@ class JpegImageStage(ImageStage):
             s.table_np[self.batch * REC_INTS:] = pre.reshape(-1)
             s.coef[:s.jused].copy_(s.coef_pin[:s.jused], non_blocking=True)
             s.table.copy_(s.table_pin, non_blocking=True)
+            if self.stream_bytes:
+                sr = s.srecords
+                lanes = np.where(sr[:, 0] == 1, sr[:, 9].astype(np.int64) * sr[:, 5], 0)
+                np.cumsum(lanes, out=pre[0, 1:])
+                if pre[0].max() > 0x7fffffff:
+                    raise ValueError("JpegImageStage.commit: more than 2^31 - 1 groups in one batch")
+                s.stable_np[self.batch * SREC_INTS:] = pre[0]
+                s.stream[:s.sused].copy_(s.stream_pin[:s.sused], non_blocking=True)
+                s.stable.copy_(s.stable_pin, non_blocking=True)
+                self.staged_stream_bytes = s.sused
             self.last_jpeg_fallbacks = s.jfallbacks
             self.staged_coef_bytes = s.jused if self.coef_format == "packed" else 2 * s.jused
             super().commit()
@@ -397,10 +589,22 @@ class JpegImageStage(ImageStage):
                                             ne, b, st), "fv_jpeg_idct_packed")
         else:
             ne = ctypes.c_longlong(self.coef_elems)
+            if self.stream_bytes:
+                L.check(lib.fv_jpeg_huff(L.ptr(s.stream), ctypes.c_longlong(self.stream_bytes), L.ptr(s.stable), L.ptr(s.coef), ne, b, st),
+                        "fv_jpeg_huff")
             L.check(lib.fv_jpeg_idct(L.ptr(s.coef), ne, L.ptr(s.table), L.ptr(self._planes), ne, b, st), "fv_jpeg_idct")
         L.check(lib.fv_jpeg_rgb(L.ptr(self._planes), ne, L.ptr(s.table), L.ptr(s.pool), ctypes.c_longlong(self.capacity), b, st),
                 "fv_jpeg_rgb")
         self._record(s)
+
+    def stream_status(self):
+        """The status word of every sample of the slot committed last, as ``fv_jpeg_huff`` left them: (batch,) int32 on the
+        host, 0 for a sample whose lanes all finished (1: bad Huffman code, 2: run past 63, 3: coefficient capacity, 4: a
+        record or entry that does not fit).  A device-to-host copy: for diagnosis, not for the step path."""
+        s = self._ready
+        if s is None or not self.stream_bytes:
+            raise RuntimeError("JpegImageStage.stream_status: no indexed batch was committed")
+        return s.stable[:self.batch * SREC_INTS].view(self.batch, SREC_INTS)[:, 24].cpu()
 
     def region(self, i):
         """The (h, w, 3) uint8 device view of sample ``i``'s source rectangle in the pool of the slot committed last."""

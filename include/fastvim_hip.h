@@ -91,7 +91,10 @@ const char* fv_last_error(void);
  *      unchanged.
  *      Later, still 3: fv_jpeg_entropy_decode_packed, fv_jpeg_packed_bound and fv_jpeg_idct_packed were ADDED (the packed
  *      coefficient form: a mask and the non-zero values per block); fv_jpeg_rgb also reads records of packed jobs; no
- *      signature changed. */
+ *      signature changed.
+ *      Later, still 3: fv_jpeg_index_bound, fv_jpeg_build_index, fv_jpeg_index_stage, fv_jpeg_stream_table_ints and
+ *      fv_jpeg_huff were ADDED (device-side Huffman decoding from a per-file index: THE INDEX below); no existing entry
+ *      point, record layout or default changed. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -1266,6 +1269,72 @@ int fv_randaug_apply(const void* in, void* out, const int* plan, const void* ws,
  *   checked against `pool_bytes` (values against its whole 4-byte words: they are read as aligned words) and every plane
  *   store against `plane_bytes`; a record or a block that does not fit is skipped.  No atomics.  `pool` 16-byte aligned, `planes` 8.  fv_jpeg_rgb reads planes only and takes the records of
  *   either form.
+ *
+ * THE INDEX (opt-in; nothing above changes).  Huffman decoding is serial only because nobody knows where MCU n starts in
+ * the bit stream and what the DC predictors are there.  A file that is read every epoch is decoded once on the host into
+ * a sidecar index that records both for every GROUP -- S = segment_mcus consecutive MCUs of one MCU row, the last group
+ * of a row shorter -- and from then on the device decodes each group on its own, one lane per group
+ * (csrc/jpeg_huff_core.h is the decoder, the same text on host and device), and the host only copies bytes.  A crop
+ * touches only the groups that meet its MCU window.  Indexed: what fv_jpeg_probe serves, without a restart interval
+ * (FV_JPEG_R_RESTART) and with one pair of Huffman tables for both chroma components (FV_JPEG_R_CHROMA_TABLES), in a
+ * file of less than 2^31 bytes.  The index is one little-endian blob of 32-bit words:
+ *     [0]        FV_JPEG_INDEX_MAGIC          [1] FV_JPEG_INDEX_VERSION
+ *     [2] [3]    bytes of the file, low and high     [4] [5] FNV-1a 64-bit hash of the file's bytes, low and high
+ *     [6] [7]    image height, width          [8] sampling class          [9] components
+ *     [10] [11]  MCUs per row, MCU rows       [12] S        [13] groups per row, ceil([10] / S)       [14] groups, [13] * [11]
+ *     [16] [17]  offset of the first entropy-coded byte, low and high       [15], [18..31] 0
+ *     [32..223]  the quantisation table of each component, 64 words, natural order: words [32..223] of the record
+ *     [224..1647] four Huffman tables of 356 words -- DC of component 0, DC of the chroma components, AC of component 0,
+ *                AC of chroma (a one-component file repeats its own) -- each as the device reads it:
+ *                  words 0..255    512 uint16: index = the next 9 bits of the stream; length << 8 | symbol of a code of at
+ *                                  most 9 bits, 0 for a longer one
+ *                  words 256..273  maxcode[0..17], int32: the largest code of each length, -1: none; [17] = 2^31 - 1
+ *                  words 274..290  valoff[0..16], int32: index of the first symbol of a length minus its first code
+ *                  word 291        symbols                words 292..355  the symbols, bytes
+ *     [1648 ..]  one ENTRY of four words per group, in file order (MCU row after MCU row), then one more, the END SENTINEL
+ *                (the position behind the last MCU): byte, bit, DC predictors of components 0 and 1 as int16 in the low
+ *                and high half, predictor of component 2 as int16 in the low half
+ *   An entry's position is that of the group's first bit in the byte-stuffed stream: `byte` is the offset IN THE FILE of
+ *   the data byte that holds it, `bit` (0..7, the most significant first) the bits of that byte that belong to the group
+ *   before.  It moves over whole stuffed bytes -- a data 0xFF and its stuffed 0x00 are one step -- so it never rests on a
+ *   stuffed 0x00; the end sentinel may rest on the marker that ends the scan.  The predictors are those before the group.
+ * fv_jpeg_index_bound(mcus_x, mcus_y, segment_mcus): the bytes of an index, FV_JPEG_INDEX_HEAD_BYTES + 16 * (groups + 1);
+ *   0 outside 1 <= mcus <= 8192 per axis, 1 <= segment_mcus <= 65536.
+ * fv_jpeg_build_index(data, nbytes, segment_mcus, out, out_capacity_bytes): host, no state.  Returns the bytes written, or
+ *   a negative code and an unspecified `out`: FV_JPEG_E_UNSERVED for a file that is not indexed -- the first int32 of `out`
+ *   then holds the FV_JPEG_R_* reason (out_capacity_bytes >= 4) -- FV_JPEG_E_CAPACITY, or the decoder's code for a stream
+ *   it gives up on (fill bytes inside the scan are among them: FV_JPEG_E_TRUNCATED).  Such files keep
+ *   fv_jpeg_entropy_decode.
+ * fv_jpeg_index_stage(data, nbytes, index, index_bytes, window, verify, pool, pool_capacity_bytes, pool_used, coef_base,
+ *   record, stream_record): host, no state, no Huffman code decoded.  Checks the index against the file -- magic, version
+ *   and the header's consistency (FV_JPEG_E_INDEX_FORMAT), nbytes and, with `verify`, the hash (FV_JPEG_E_INDEX_FILE), the
+ *   window (FV_JPEG_E_WINDOW), and that every entry it will use, the one behind each row's last group included, lies
+ *   inside the scan with bit <= 7 and in file order (FV_JPEG_E_INDEX_ENTRY) -- then appends to the host stream pool `pool`
+ *   (16-byte aligned) from the next multiple of 16 at or above *pool_used: the four tables, the entries of the groups
+ *   that meet the window (row after row of the window, `group columns` per row), and the bytes of the file from the
+ *   first of those groups to two bytes past the start of the group behind the last (clamped to the file), zero-padded to
+ *   16.  FV_JPEG_E_CAPACITY without a write if that does not fit; *pool_used is advanced.  Writes the ordinary dense record
+ *   ([0] = 1; [18] = the MCUs fv_jpeg_entropy_decode would have decoded; [19..24] are the caller's as ever) whose
+ *   component offsets are `coef_base` (elements, a multiple of 8: where the caller reserved the window's coefficients)
+ *   plus the decoder's, and the STREAM RECORD, FV_JPEG_STREAM_REC_INTS int32:
+ *     [0]        1: an indexed job (0: none)          [1] sampling class
+ *     [2..5]     the window: x0, y0, w, h in MCUs     [6] MCUs per row of the image      [7] S
+ *     [8] [9]    the first group column the window meets, and how many
+ *     [10..15]   per component the offset of its coefficients in the coefficient pool, elements, low and high
+ *     [16] [17]  byte offset of the tables in the stream pool, [18] [19] of the entries, [20] [21] of the file bytes
+ *     [22]       file bytes staged       [23] offset in the file of the first of them
+ *     [24]       DEVICE: the status, 0 or the FV_JPEG_ST_* of a lane that gave up        [25..31] 0
+ * fv_jpeg_stream_table_ints(batch): the words of the STREAM TABLE in device memory: `batch` stream records, then
+ *   batch + 1 int32 prefix sums of the records' lanes ([9] * [5], 0 for a record with [0] == 0).
+ * fv_jpeg_huff(stream_pool, stream_bytes, stream_table, coef, coef_elems, batch, stream): in front of fv_jpeg_idct.  One
+ *   lane per group: it finds its sample by a search over the prefix sums, decodes the group's MCUs from its entry and
+ *   writes all 64 coefficients, zeros included, of every block inside the window where fv_jpeg_entropy_decode would have
+ *   put them; blocks outside the window are decoded and dropped.  Every block of a window belongs to exactly one lane: no
+ *   memset, no atomics, and a replay never sees stale coefficients.  The grid is from stream_bytes alone (a lane needs a
+ *   16-byte entry).  Every table, entry and stream read is checked against stream_bytes (the stream against the staged
+ *   range; beyond it and from a marker on the reader delivers zero bits), every store against coef_elems, and every loop
+ *   is bounded independently of the stream: a corrupt stream or index gives unspecified coefficients and a non-zero
+ *   status word ([24], a plain store), never a hang or an access out of range.  stream_pool and coef 16-byte aligned.
  * ---------------------------------------------------------------------- */
 #define FV_JPEG_INFO_INTS 8
 #define FV_JPEG_REC_INTS 224
@@ -1304,6 +1373,27 @@ int fv_jpeg_entropy_decode_packed(const void* data, long long nbytes, const int*
                                   long long out_capacity_bytes, int* record);
 int fv_jpeg_idct_packed(const void* pool, long long pool_bytes, const int* table, void* planes, long long plane_bytes,
                         int batch, fv_stream_t stream);
+#define FV_JPEG_INDEX_MAGIC 0x58494A46u
+#define FV_JPEG_INDEX_VERSION 1
+#define FV_JPEG_INDEX_HEAD_BYTES 6592
+#define FV_JPEG_STREAM_REC_INTS 32
+#define FV_JPEG_R_RESTART 11
+#define FV_JPEG_R_CHROMA_TABLES 12
+#define FV_JPEG_E_INDEX_FORMAT (-17)
+#define FV_JPEG_E_INDEX_FILE (-18)
+#define FV_JPEG_E_INDEX_ENTRY (-19)
+#define FV_JPEG_ST_CODE 1
+#define FV_JPEG_ST_RUN 2
+#define FV_JPEG_ST_CAPACITY 3
+#define FV_JPEG_ST_RECORD 4
+long long fv_jpeg_index_bound(int mcus_x, int mcus_y, int segment_mcus);
+long long fv_jpeg_build_index(const void* data, long long nbytes, int segment_mcus, void* out, long long out_capacity_bytes);
+int fv_jpeg_index_stage(const void* data, long long nbytes, const void* index, long long index_bytes, const int* window,
+                        int verify, void* pool, long long pool_capacity_bytes, long long* pool_used, long long coef_base,
+                        int* record, int* stream_record);
+long long fv_jpeg_stream_table_ints(int batch);
+int fv_jpeg_huff(const void* stream_pool, long long stream_bytes, int* stream_table, void* coef, long long coef_elems,
+                 int batch, fv_stream_t stream);
 
 #ifdef __cplusplus
 }
