@@ -48,6 +48,7 @@ C_ABI_SYMBOLS = (
     "fv_jpeg_packed_bound", "fv_jpeg_entropy_decode_packed", "fv_jpeg_idct_packed",
     "fv_mae_noise", "fv_mae_mask_plan_keyed",
     "fv_jpeg_index_bound", "fv_jpeg_build_index", "fv_jpeg_index_stage", "fv_jpeg_stream_table_ints", "fv_jpeg_huff",
+    "fv_cellaug_geom", "fv_cellaug_filter",
 )
 
 

@@ -94,7 +94,9 @@ const char* fv_last_error(void);
  *      signature changed.
  *      Later, still 3: fv_jpeg_index_bound, fv_jpeg_build_index, fv_jpeg_index_stage, fv_jpeg_stream_table_ints and
  *      fv_jpeg_huff were ADDED (device-side Huffman decoding from a per-file index: THE INDEX below); no existing entry
- *      point, record layout or default changed. */
+ *      point, record layout or default changed.
+ *      Later, still 3: fv_cellaug_geom and fv_cellaug_filter were ADDED (the cell-image augmentation of the channel
+ *      models' loader on planar uint8 planes: THE CELL RECORD below); no existing entry point changed. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -1394,6 +1396,58 @@ int fv_jpeg_index_stage(const void* data, long long nbytes, const void* index, l
 long long fv_jpeg_stream_table_ints(int batch);
 int fv_jpeg_huff(const void* stream_pool, long long stream_bytes, int* stream_table, void* coef, long long coef_elems,
                  int batch, fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Device-side cell-image augmentation: the pixel work of the reference's CellAugmentation(is_train=True)
+ * (cell_imaging/transformations/cell.py:104-149) in front of A.Normalize (fv_patch_unfold_chan_u8): pad + crop, one of
+ * {horizontal flip, vertical flip, rotation by any angle}, defocus, coarse dropout.  The host draws and turns every draw
+ * into numbers (fastvim_amd/cellaug.py); the device applies them.  The arithmetic below is the contract; it is restated in
+ * numpy at tests/cellaug_ref.py.
+ *
+ *   pool   uint8, `pool_bytes` long: the sources back to back, each (channels, H, W) planar with packed rows; a source
+ *          may start at any byte (fastvim_amd/cellaug.py starts each on a 16-byte boundary).
+ *   plan   (batch, FV_CELLAUG_PLAN_INTS) int32 in DEVICE memory, 8-byte aligned, read when the kernels RUN.
+ *          THE CELL RECORD, per sample:
+ *            [0] [1]      byte offset of the source in the pool, low and high 32 bits
+ *            [2] [3]      H, W of the source, each in [1, 4096]
+ *            [4] [5]      oy, ox: crop pixel (y, x) is src[c][y - oy][x - ox] inside the source and 0 outside
+ *                         (oy = pad_top - crop_top, likewise ox; |oy|, |ox| <= 8192)
+ *            [6]          geometry: FV_CELLAUG_NONE, _HFLIP (out[y][x] = crop[y][S-1-x]), _VFLIP (crop[S-1-y][x]), _ROTATE
+ *            [7]          defocus != 0: correlate with the kernel at [24..104]
+ *            [8]          number of holes, 0 .. FV_CELLAUG_MAX_HOLES
+ *            [9..11]      unused, 0
+ *            [12..23]     m0 .. m5, six fp64 (low word first): the INVERSE (destination to source) affine map of a
+ *                         rotation, sx = m0 x + m1 y + m2, sy = m3 x + m4 y + m5
+ *            [24..104]    the 9 x 9 defocus kernel, fp32 bits, row-major
+ *            [105..107]   unused, 0
+ *            [108..171]   the holes, four words each: y1, x1, y2, x2 (y2, x2 exclusive) in output coordinates
+ *            [172..175]   unused, 0
+ *   out    (batch, channels, S, S) uint8, planar, contiguous; 4-byte stores when S % 4 == 0 and the buffers allow them.
+ *
+ * fv_cellaug_geom: pool -> out.  A rotation is the fixed-point scheme of an 8-bit bilinear warpAffine; after the fp64
+ *   products (no contraction) everything is integer:
+ *     adelta[x] = rint(m0 x 1024), bdelta[x] = rint(m3 x 1024)
+ *     X0[y] = rint((m1 y + m2) 1024) + 16,  Y0[y] = rint((m4 y + m5) 1024) + 16
+ *     X = (X0 + adelta) >> 5, sx = X >> 5, fx = X & 31; the same for Y
+ *     taps (sy, sx), (sy, sx+1), (sy+1, sx), (sy+1, sx+1), each index reflected (REFLECT_101: 2 1 | 0 1 2 ..) within the
+ *     S x S crop and only then mapped to the source; weights (32-fy)(32-fx)32, (32-fy)fx 32, fy(32-fx)32, fy fx 32
+ *     out = (sum w p + 16384) >> 15
+ * fv_cellaug_filter: in -> out, both (batch, channels, S, S) and not overlapping.  With defocus, out = clamp(rint(acc), 0,
+ *   255) where acc runs over the 81 taps in row-major order, skipping weights that are exactly 0, in fp32 with the product
+ *   and the add rounded separately (no FMA), borders REFLECT_101; without, a copy.  Then 0 inside each hole.
+ * Both serve batch in [1, 4096], channels in [1, 16], S in [8, 512].  A record outside the ranges above, or whose source
+ * does not lie inside the pool, reads nothing and gives zeros.  No atomics; every output byte has one owner.
+ * ---------------------------------------------------------------------- */
+#define FV_CELLAUG_PLAN_INTS 176
+#define FV_CELLAUG_TAPS 9
+#define FV_CELLAUG_MAX_HOLES 16
+#define FV_CELLAUG_NONE 0
+#define FV_CELLAUG_HFLIP 1
+#define FV_CELLAUG_VFLIP 2
+#define FV_CELLAUG_ROTATE 3
+int fv_cellaug_geom(const void* pool, long long pool_bytes, const int* plan, void* out, int batch, int channels, int size,
+                    fv_stream_t stream);
+int fv_cellaug_filter(const void* in, const int* plan, void* out, int batch, int channels, int size, fv_stream_t stream);
 
 #ifdef __cplusplus
 }
