@@ -49,6 +49,7 @@ C_ABI_SYMBOLS = (
     "fv_mae_noise", "fv_mae_mask_plan_keyed",
     "fv_jpeg_index_bound", "fv_jpeg_build_index", "fv_jpeg_index_stage", "fv_jpeg_stream_table_ints", "fv_jpeg_huff",
     "fv_cellaug_geom", "fv_cellaug_filter",
+    "fv_jpeg_sync_stage", "fv_jpeg_sync_host", "fv_jpeg_sync_table_ints", "fv_jpeg_sync",
 )
 
 
@@ -104,6 +105,7 @@ def lib():
         cdll.fv_jpeg_index_bound.restype = ctypes.c_longlong
         cdll.fv_jpeg_build_index.restype = ctypes.c_longlong
         cdll.fv_jpeg_stream_table_ints.restype = ctypes.c_longlong
+        cdll.fv_jpeg_sync_table_ints.restype = ctypes.c_longlong
         _lib = _DeviceGuarded(cdll)
     return _lib
 

@@ -1,6 +1,6 @@
 // The host half of the JPEG decode (include/fastvim_hip.h at fv_jpeg_probe): marker parser and Huffman decoder of baseline
 // JPEG files, plain C++ with nothing from HIP -- the file also compiles on its own with the host compiler
-// (tools/jpeg_host_check.cpp, tools/jpeg_packed_check.cpp and tools/jpeg_index_check.cpp run it under the address and
+// (tools/jpeg_host_check.cpp, tools/jpeg_packed_check.cpp, tools/jpeg_index_check.cpp and tools/jpeg_sync_check.cpp run it under the address and
 // undefined-behaviour sanitizers).  No shared state -- the packed entry point keeps a scratch buffer per thread: any number of loader threads
 // may decode at once.  Every read is checked against [data, data + nbytes), every write against
 // coef_out[0 : coef_capacity]; an anomaly is an error code, never a partial result.
@@ -14,6 +14,7 @@
 
 #include "../../include/fastvim_hip.h"
 #include "jpeg_huff_core.h"
+#include "jpeg_sync_core.h"
 
 namespace {
 
@@ -523,6 +524,23 @@ void pack_table(const Huff& h, uint32_t* t) {
   memcpy(t + fvhuff::T_VALS, h.vals, (size_t)h.nvals);
 }
 
+// the four tables of a file in the order the device reads them
+void pack_tables(const Frame& f, uint32_t* tables) {
+  const int cc = f.ncomp == 3 ? 1 : 0;
+  pack_table(f.huff[0][f.td[0]], tables);
+  pack_table(f.huff[0][f.td[cc]], tables + fvhuff::TABLE_WORDS);
+  pack_table(f.huff[1][f.ta[0]], tables + 2 * fvhuff::TABLE_WORDS);
+  pack_table(f.huff[1][f.ta[cc]], tables + 3 * fvhuff::TABLE_WORDS);
+}
+
+// why a parsed file gets no entries (index or sync), or FV_JPEG_R_OK
+int indexed_reason(const Frame& f) {
+  if (f.reason != FV_JPEG_R_OK) return f.reason;
+  if (f.ri) return FV_JPEG_R_RESTART;
+  if (f.ncomp == 3 && (f.td[1] != f.td[2] || f.ta[1] != f.ta[2])) return FV_JPEG_R_CHROMA_TABLES;
+  return FV_JPEG_R_OK;
+}
+
 struct Index {
   const uint8_t* p;
   int H, W, cls, ncomp, mcus_x, mcus_y, S, gpr;
@@ -564,9 +582,7 @@ extern "C" long long fv_jpeg_build_index(const void* data, long long nbytes, int
   Frame f;
   const uint8_t* d = (const uint8_t*)data;
   parse(d, nbytes, f);
-  int reason = f.reason;
-  if (reason == FV_JPEG_R_OK && f.ri) reason = FV_JPEG_R_RESTART;
-  if (reason == FV_JPEG_R_OK && f.ncomp == 3 && (f.td[1] != f.td[2] || f.ta[1] != f.ta[2])) reason = FV_JPEG_R_CHROMA_TABLES;
+  const int reason = indexed_reason(f);
   if (reason != FV_JPEG_R_OK) {
     if (out_capacity_bytes >= 4) memcpy(out, &reason, 4);
     return FV_JPEG_E_UNSERVED;
@@ -590,11 +606,7 @@ extern "C" long long fv_jpeg_build_index(const void* data, long long nbytes, int
   // the tables the walk below reads are the ones that go into the index
   uint32_t* tables = (uint32_t*)malloc(sizeof(uint32_t) * IDX_TABLE_WORDS);
   if (!tables) return FV_JPEG_E_CAPACITY;
-  const int cc = f.ncomp == 3 ? 1 : 0;
-  pack_table(f.huff[0][f.td[0]], tables);
-  pack_table(f.huff[0][f.td[cc]], tables + fvhuff::TABLE_WORDS);
-  pack_table(f.huff[1][f.ta[0]], tables + 2 * fvhuff::TABLE_WORDS);
-  pack_table(f.huff[1][f.ta[cc]], tables + 3 * fvhuff::TABLE_WORDS);
+  pack_tables(f, tables);
   uint8_t* o = (uint8_t*)out;
   memcpy(o, head, sizeof(head));
   memcpy(o + sizeof(head), tables, sizeof(uint32_t) * IDX_TABLE_WORDS);
@@ -702,5 +714,164 @@ extern "C" int fv_jpeg_index_stage(const void* data, long long nbytes, const voi
   put_i64(stream_record, 20, base + tbytes + 16 * lanes);
   stream_record[22] = (int)len;
   stream_record[23] = (int)first;
+  return FV_OK;
+}
+
+// --------------------------------------------------------------------------------------- ENTRIES MADE ON THE DEVICE
+// include/fastvim_hip.h at ENTRIES MADE ON THE DEVICE.  The host parses markers and copies; the entries are found by the
+// passes of jpeg_sync_core.h -- on the device by fv_jpeg_sync (jpeg_sync.hip), here serially by fv_jpeg_sync_host.
+static_assert(FV_JPEG_SYNC_JOB_INTS == fvsync::JOB_INTS && FV_JPEG_ST_SYNC_JOB == fvsync::ST_JOB && FV_JPEG_ST_SYNC_LOST == fvsync::ST_LOST &&
+              FV_JPEG_SYNC_REC_BYTES == 4 * fvsync::REC_WORDS && FV_JPEG_SYNC_MAX_SUBSEQS == fvsync::MAX_SUBSEQS,
+              "the sync core and the header agree");
+
+extern "C" int fv_jpeg_sync_stage(const void* data, long long nbytes, const int* window, int segment_mcus, int subseq_bytes,
+                                  long long max_scan_bytes, void* pool, long long pool_capacity_bytes, long long* pool_used,
+                                  long long scratch_capacity_records, long long* scratch_used, long long coef_base, int* record,
+                                  int* stream_record, int* job) {
+  if (!data || !window || !pool || !pool_used || !scratch_used || !record || !stream_record || !job || nbytes < 0 ||
+      pool_capacity_bytes < 0 || *pool_used < 0 || scratch_capacity_records < 0 || *scratch_used < 0 || coef_base < 0 ||
+      (coef_base & 7) || ((uintptr_t)pool & 15) || segment_mcus < 1 || segment_mcus > IDX_MAX_S || subseq_bytes < fvsync::MIN_SUBSEQ ||
+      subseq_bytes > fvsync::MAX_SUBSEQ || (subseq_bytes & (subseq_bytes - 1)) || max_scan_bytes < 0)
+    return FV_ERR_INVALID;
+  Frame f;
+  const uint8_t* d = (const uint8_t*)data;
+  parse(d, nbytes, f);
+  const int reason = indexed_reason(f);
+  if (reason != FV_JPEG_R_OK) {
+    job[0] = 0;
+    job[1] = reason;
+    return FV_JPEG_E_UNSERVED;
+  }
+  if (nbytes > 0x7fffffff) return FV_JPEG_E_CAPACITY;
+  Window w;
+  int rc = window_of(f, window, w);
+  if (rc != FV_OK) return rc;
+  // the scan ends in front of the first 0xFF that no 0x00 follows.  Fill bytes in front of a stuffed 0x00 or a restart
+  // marker continue it in a way the device reader does not follow: the index builder gives such a file up as well
+  long long end = f.scan;
+  while (end < nbytes && !(d[end] == 0xFF && (end + 1 >= nbytes || d[end + 1] != 0))) end += d[end] == 0xFF ? 2 : 1;
+  if (end > nbytes) end = nbytes;
+  if (end < nbytes) {
+    long long p = end;
+    while (p + 1 < nbytes && d[p + 1] == 0xFF) ++p;
+    if (p > end && p + 1 < nbytes && (d[p + 1] == 0 || (d[p + 1] >= 0xD0 && d[p + 1] <= 0xD7))) return FV_JPEG_E_TRUNCATED;
+  }
+  const long long len = end - f.scan;
+  if (len < 1) return FV_JPEG_E_TRUNCATED;
+  const long long cap = max_scan_bytes < fvsync::MAX_SCAN ? max_scan_bytes : fvsync::MAX_SCAN;
+  if (len > cap || (len + subseq_bytes - 1) / subseq_bytes > fvsync::MAX_SUBSEQS) return FV_JPEG_E_SCAN_SIZE;
+  const int S = segment_mcus, L = subseq_bytes;
+  const int gx0 = w.x0 / S, gx1 = (w.x0 + w.mw - 1) / S, gw = gx1 - gx0 + 1;
+  const long long lanes = (long long)gw * w.mh, len16 = (len + 15) / 16 * 16, nsub = (len + L - 1) / L;
+  const long long base = (*pool_used + 15) / 16 * 16, tbytes = 4ll * IDX_TABLE_WORDS;
+  if (base + tbytes + 16 * lanes + len16 > pool_capacity_bytes || *scratch_used + nsub > scratch_capacity_records) return FV_JPEG_E_CAPACITY;
+  uint8_t* o = (uint8_t*)pool + base;
+  pack_tables(f, (uint32_t*)o);
+  memset(o + tbytes, 0xFF, (size_t)(16 * lanes));      // an entry nobody wrote: bit > 7, fv_jpeg_huff's lane gives ST_RECORD
+  memcpy(o + tbytes + 16 * lanes, d + f.scan, (size_t)len);
+  memset(o + tbytes + 16 * lanes + len, 0, (size_t)(len16 - len));
+  const long long roff = *scratch_used;
+  *pool_used = base + tbytes + 16 * lanes + len16;
+  *scratch_used = roff + nsub;
+
+  const long long mcus = (long long)(w.y0 + w.mh - 1) * f.mcus_x + w.x0 + w.mw;
+  common_record(f, w, mcus, 1, record);
+  memset(stream_record, 0, sizeof(int) * FV_JPEG_STREAM_REC_INTS);
+  for (int c = 0; c < f.ncomp; ++c) {
+    put_i64(record, 9 + 2 * c, coef_base + w.first[c] * 64);
+    put_i64(stream_record, 10 + 2 * c, coef_base + w.first[c] * 64);
+  }
+  put_i64(record, 15, w.blocks * 64);
+  stream_record[0] = 1;
+  stream_record[1] = f.cls;
+  stream_record[2] = w.x0; stream_record[3] = w.y0; stream_record[4] = w.mw; stream_record[5] = w.mh;
+  stream_record[6] = f.mcus_x;
+  stream_record[7] = S;
+  stream_record[8] = gx0; stream_record[9] = gw;
+  put_i64(stream_record, 16, base);
+  put_i64(stream_record, 18, base + tbytes);
+  put_i64(stream_record, 20, base + tbytes + 16 * lanes);
+  stream_record[22] = (int)len;
+  stream_record[23] = (int)f.scan;
+  memset(job, 0, sizeof(int) * FV_JPEG_SYNC_JOB_INTS);
+  job[0] = 1;
+  job[1] = f.cls;
+  job[2] = w.x0; job[3] = w.y0; job[4] = w.mw; job[5] = w.mh;
+  job[6] = f.mcus_x;
+  job[7] = S;
+  job[8] = gx0; job[9] = gw;
+  put_i64(job, 10, base + tbytes + 16 * lanes);
+  job[12] = (int)len;
+  job[13] = (int)f.scan;
+  job[14] = 0;
+  job[15] = L;
+  job[16] = (int)nsub;
+  put_i64(job, 17, base + tbytes);
+  put_i64(job, 19, base);
+  put_i64(job, 21, roff);
+  job[23] = f.mcus_y;
+  return FV_OK;
+}
+
+extern "C" int fv_jpeg_sync_host(void* pool, long long pool_bytes, int* job, void* scratch, long long scratch_records) {
+  if (!pool || !job || !scratch || pool_bytes < 0 || scratch_records < 0 || ((uintptr_t)pool & 15) || ((uintptr_t)scratch & 3))
+    return FV_ERR_INVALID;
+  if (job[0] != 1) return FV_OK;
+  fvsync::Job J;
+  if (!fvsync::open_job(job, pool_bytes, scratch_records, J)) {
+    job[fvsync::JOB_STATUS] = fvsync::ST_JOB;
+    return FV_OK;
+  }
+  uint8_t* p = (uint8_t*)pool;
+  const uint8_t* d = p + J.soff;
+  const uint32_t* tables = (const uint32_t*)(p + J.toff);
+  uint32_t* recs = (uint32_t*)scratch + J.roff * fvsync::REC_WORDS;
+  for (uint32_t i = 0; i < J.nsub; ++i) fvsync::pass_speculate(J, d, tables, recs, i);
+  // what speculation was worth (words [26..28], this function only): the speculative exit states are kept for that
+  uint32_t* spec = (uint32_t*)malloc(sizeof(uint32_t) * 2 * (size_t)J.nsub);
+  for (uint32_t i = 0; spec && i < J.nsub; ++i) memcpy(spec + 2 * i, recs + (size_t)i * fvsync::REC_WORDS, 8);
+  int rounds = 0;
+  for (uint32_t r = 0; r < J.nsub; ++r) {
+    bool any = false;
+    for (uint32_t i = 0; i < J.nsub; ++i) any |= fvsync::round_take(recs, i);
+    if (!any) break;
+    for (uint32_t i = 0; i < J.nsub; ++i) fvsync::round_decode(J, d, tables, recs, i);
+    ++rounds;
+  }
+  if (spec) {
+    int dead = 0, wrong = 0, run = 0, longest = 0;
+    for (uint32_t i = 0; i + 1 < J.nsub; ++i) {                   // the last exit state lies behind the last MCU
+      const uint32_t* rec = recs + (size_t)i * fvsync::REC_WORDS;
+      const bool inv = spec[2 * i] == fvsync::INVALID && rec[0] != fvsync::INVALID;
+      dead += inv;
+      wrong += !inv && (spec[2 * i] != rec[0] || spec[2 * i + 1] != rec[1]);
+      run = inv ? run + 1 : 0;
+      longest = run > longest ? run : longest;
+    }
+    job[26] = dead; job[27] = wrong; job[28] = longest;
+    free(spec);
+  }
+  // the scan: counts and sums become the first MCU start and the predictors at each subsequence's entry; the MCU starts
+  // that count are those in front of the first INVALID exit state
+  fvsync::Prefix valid{0u, 0u};
+  uint32_t first = 0, dc[3] = {0, 0, 0};
+  for (uint32_t i = 0; i < J.nsub; ++i) {
+    uint32_t* rec = recs + (size_t)i * fvsync::REC_WORDS;
+    const uint32_t n = rec[4], s01 = rec[5], s2 = rec[6];
+    valid = fvsync::join(valid, fvsync::prefix_of(rec));
+    rec[4] = first;
+    rec[5] = (dc[0] & 0xffffu) | (dc[1] & 0xffffu) << 16;
+    rec[6] = dc[2] & 0xffffu;
+    first += n;
+    dc[0] += s01 & 0xffffu; dc[1] += s01 >> 16; dc[2] += s2 & 0xffffu;
+  }
+  job[fvsync::JOB_ROUNDS] = rounds;
+  if ((long long)valid.n <= fvsync::last_needed(J)) {
+    job[fvsync::JOB_STATUS] = fvsync::ST_LOST;
+    return FV_OK;
+  }
+  for (uint32_t i = 0; i < J.nsub; ++i)
+    fvsync::pass_emit(J, d, tables, recs, i, i + 1 < J.nsub ? recs[(size_t)(i + 1) * fvsync::REC_WORDS + 4] : first, p);
+  job[fvsync::JOB_STATUS] = 0;
   return FV_OK;
 }

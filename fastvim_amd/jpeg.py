@@ -29,7 +29,16 @@ decodes the Huffman codes too, one lane per group (``fv_jpeg_huff``); the host o
 
     idx = jpeg.build_index(raw)                            # once per file, kept next to it
     stage = JpegImageStage(B, 224, capacity_bytes=B << 20, coef_capacity_bytes=B << 21, stream_capacity_bytes=B << 17)
-    stage.put_jpeg_indexed(k, raw, idx, crop=(i, j, h, w), flip=f)"""
+    stage.put_jpeg_indexed(k, raw, idx, crop=(i, j, h, w), flip=f)
+
+FILES WITHOUT AN INDEX (opt-in): a stage built with ``sync=True`` takes any ``.jpg`` through ``put_jpeg_sync``.  The host
+parses the markers and copies the whole scan; the device finds the group starts itself (``fv_jpeg_sync``: the scan is cut
+into subsequences of ``subseq_bytes``, each decoded speculatively and again from its predecessor's exit state until nothing
+changes) and writes the entries ``fv_jpeg_huff`` then starts from.  A file the index builder would refuse takes the
+``put_jpeg`` route inside the same call::
+
+    stage = JpegImageStage(B, 224, capacity_bytes=B << 20, coef_capacity_bytes=B << 21, stream_capacity_bytes=B << 18, sync=True)
+    stage.put_jpeg_sync(k, raw, crop=(i, j, h, w), flip=f)"""
 import ctypes
 import io
 import threading
@@ -56,6 +65,11 @@ INDEX_ERRORS = {-15: "capacity", -17: "not an index of this version, or an incon
 INDEX_MAGIC, INDEX_VERSION, INDEX_HEAD_BYTES = 0x58494A46, 1, 6592
 SREC_INTS = 32            # FV_JPEG_STREAM_REC_INTS
 DEFAULT_SEGMENT_MCUS = 1  # S: MCUs per group; the S of the lowest fv_jpeg_huff time in profiles/jpeg_index_bench.log
+SYNC_JOB_INTS, SYNC_REC_BYTES = 32, 32    # FV_JPEG_SYNC_JOB_INTS, FV_JPEG_SYNC_REC_BYTES
+SYNC_MAX_SUBSEQS = 16384                  # FV_JPEG_SYNC_MAX_SUBSEQS
+DEFAULT_SUBSEQ_BYTES = 128                # the subseq_bytes of the lowest fv_jpeg_sync time in profiles/jpeg_sync_bench.log
+SYNC_STATUS = {5: "a sync job that does not fit its buffers", 6: "an exit state stays INVALID before the last group start needed"}
+SYNC_REFUSALS = (-10, -11, -20)           # unserved or not indexable, fill bytes inside the scan, a scan above max_scan_bytes
 _MCU = ((1, 1), (2, 1), (2, 2), (1, 1))  # (h_max, v_max) of a sampling class
 
 
@@ -251,6 +265,40 @@ def index_stage(raw, index, window=None, verify=False):
     return rec, srec, pool[:used.value].copy()
 
 
+def sync_stage(raw, window=None, segment_mcus=DEFAULT_SEGMENT_MCUS, subseq_bytes=DEFAULT_SUBSEQ_BYTES, max_scan_bytes=1 << 20,
+               pool_capacity_bytes=None, run=True):
+    """The index-free path on the host alone (no GPU): ``fv_jpeg_sync_stage`` of the MCU ``window`` (default: the whole
+    image) into a fresh stream pool, then -- with ``run`` -- ``fv_jpeg_sync_host``, the passes of ``fv_jpeg_sync`` run serially
+    on the CPU.  Returns ``(record, stream_record, job, pool)``; the entries are ``pool[job[17]:][:16 * groups]``, the
+    status and the rounds ``job[24]`` and ``job[25]``.  ``ValueError`` with the code for a file or a capacity the stage
+    function refuses (``.args[1]`` is the code, ``.args[2]`` the FV_JPEG_R_* reason of an unserved file)."""
+    raw = _as_bytes(raw)
+    info = _probe(raw)
+    win = (0, 0, max(info[6], 1), max(info[7], 1)) if window is None else tuple(int(v) for v in window)
+    cap = len(raw) + 8192 + 16 * max(win[2] * win[3], 0) if pool_capacity_bytes is None else int(pool_capacity_bytes)
+    pool = _aligned_bytes(max(cap, 16))
+    before = pool.copy()
+    records = len(raw) // int(subseq_bytes) + 2 if int(subseq_bytes) > 0 else 2
+    scratch = np.zeros(records * SYNC_REC_BYTES // 4, np.uint32)
+    rec, srec, job = np.zeros(REC_INTS, np.int32), np.zeros(SREC_INTS, np.int32), np.zeros(SYNC_JOB_INTS, np.int32)
+    used, rused = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    lib = L.host_lib()
+    rc = lib.fv_jpeg_sync_stage(ctypes.c_char_p(raw), ctypes.c_longlong(len(raw)), (ctypes.c_int * 4)(*win), L.i32(segment_mcus),
+                                L.i32(subseq_bytes), ctypes.c_longlong(int(max_scan_bytes)), ctypes.c_void_p(pool.ctypes.data),
+                                ctypes.c_longlong(cap), ctypes.byref(used), ctypes.c_longlong(records), ctypes.byref(rused),
+                                ctypes.c_longlong(0), ctypes.c_void_p(rec.ctypes.data), ctypes.c_void_p(srec.ctypes.data),
+                                ctypes.c_void_p(job.ctypes.data))
+    if rc != 0:
+        assert np.array_equal(pool, before) and used.value == 0 and rused.value == 0      # a refusal leaves the pool and both counters alone (an unserved file: job[0] = 0, job[1] = the reason)
+        raise ValueError(f"fv_jpeg_sync_stage: code {rc}", rc, int(job[1]))
+    if run:
+        rc = lib.fv_jpeg_sync_host(ctypes.c_void_p(pool.ctypes.data), ctypes.c_longlong(used.value), ctypes.c_void_p(job.ctypes.data),
+                                   ctypes.c_void_p(scratch.ctypes.data), ctypes.c_longlong(records))
+        if rc != 0:
+            raise ValueError(f"fv_jpeg_sync_host: code {rc}", rc, 0)
+    return rec, srec, job, pool[:used.value].copy()
+
+
 def _pil_decode(data):
     from PIL import Image
     return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
@@ -278,10 +326,18 @@ class JpegImageStage(ImageStage):
     meets and the file bytes of those groups -- the stream table and its status words.  ``put_jpeg_indexed`` fills them;
     its coefficients never cross the link: their space is taken from the TOP of the coefficient pool downward, against
     the same ``coef_capacity_bytes``, and ``fv_jpeg_huff`` writes them in front of ``fv_jpeg_idct``.  ``segment_capacity``
-    bounds the groups (lanes) of a batch; 0: only the stream pool bounds them, 16 bytes each."""
+    bounds the groups (lanes) of a batch; 0: only the stream pool bounds them, 16 bytes each.
+
+    ``sync=True`` (default False: none of this exists; needs ``stream_capacity_bytes``) adds the INDEX-FREE path:
+    ``put_jpeg_sync`` stages the tables, a reserved entry region and the WHOLE SCAN of a file (at most ``max_scan_bytes``) in
+    the stream pool, with groups of ``segment_mcus`` MCUs, and a sync job; ``fv_jpeg_sync`` runs in front of
+    ``fv_jpeg_huff`` and writes the entries, working on subsequences of ``subseq_bytes`` (a power of two in [16, 1024];
+    default ``DEFAULT_SUBSEQ_BYTES``) whose states live in a scratch buffer the slots share, 32 bytes per subsequence the
+    stream pool can hold."""
 
     def __init__(self, batch, out_size, capacity_bytes, coef_capacity_bytes, slots=2, device=None, coef_format="dense",
-                 plane_capacity_bytes=None, stream_capacity_bytes=0, segment_capacity=0):
+                 plane_capacity_bytes=None, stream_capacity_bytes=0, segment_capacity=0, sync=False, subseq_bytes=None,
+                 max_scan_bytes=1 << 20, segment_mcus=DEFAULT_SEGMENT_MCUS):
         if coef_format not in ("dense", "packed"):
             raise ValueError(f"JpegImageStage: coef_format {coef_format!r} is neither 'dense' nor 'packed'")
         if int(stream_capacity_bytes) < 0 or int(segment_capacity) < 0:
@@ -291,6 +347,24 @@ class JpegImageStage(ImageStage):
                              "coef_format='packed' is not accepted with it")
         if int(segment_capacity) and not int(stream_capacity_bytes):
             raise ValueError("JpegImageStage: segment_capacity belongs to the indexed path (stream_capacity_bytes)")
+        self.sync = bool(sync)
+        if self.sync:
+            if coef_format != "dense":
+                raise ValueError("JpegImageStage: sync=True writes dense coefficients through fv_jpeg_huff: "
+                                 "coef_format='packed' is not accepted with it")
+            if not int(stream_capacity_bytes):
+                raise ValueError("JpegImageStage: sync=True needs stream_capacity_bytes (the scans are staged in the stream pool)")
+            self.subseq_bytes = DEFAULT_SUBSEQ_BYTES if subseq_bytes is None else int(subseq_bytes)
+            if not 16 <= self.subseq_bytes <= 1024 or self.subseq_bytes & (self.subseq_bytes - 1):
+                raise ValueError(f"JpegImageStage: subseq_bytes {self.subseq_bytes} is not a power of two in [16, 1024]")
+            self.max_scan_bytes, self.segment_mcus = int(max_scan_bytes), int(segment_mcus)
+            if self.max_scan_bytes < 1 or not 1 <= self.segment_mcus <= 65536:
+                raise ValueError("JpegImageStage: max_scan_bytes below 1 or segment_mcus outside [1, 65536]")
+            # a job has at most SYNC_MAX_SUBSEQS subsequences (the rounds of a launch are bounded by them): a longer scan is
+            # refused by the stage function like one above max_scan_bytes, and takes the put_jpeg route
+            self.max_scan_bytes = min(self.max_scan_bytes, SYNC_MAX_SUBSEQS * self.subseq_bytes)
+        elif subseq_bytes is not None or int(max_scan_bytes) != 1 << 20 or int(segment_mcus) != DEFAULT_SEGMENT_MCUS:
+            raise ValueError("JpegImageStage: subseq_bytes, max_scan_bytes and segment_mcus belong to sync=True")
         super().__init__(batch, out_size, capacity_bytes, slots=slots, device=device)
         self.coef_format = coef_format
         self._lock = threading.RLock()
@@ -300,6 +374,7 @@ class JpegImageStage(ImageStage):
         self.stream_bytes = (int(stream_capacity_bytes) + 15) // 16 * 16
         self.segment_capacity = int(segment_capacity)
         self.staged_stream_bytes = 0           # stream pool bytes of the batch committed last: tables, entries, file bytes
+        self.last_sync_fallbacks = 0           # of the batch committed last: files put_jpeg_sync sent the put_jpeg route
         n = int(L.lib().fv_jpeg_table_ints(L.i32(self.batch)))
         assert n == self.batch * REC_INTS + 2 * (self.batch + 1)
         for s in self._slots:
@@ -337,6 +412,16 @@ class JpegImageStage(ImageStage):
                 s.stable_np = s.stable_pin.numpy()
                 s.srecords = s.stable_np[:self.batch * SREC_INTS].reshape(self.batch, SREC_INTS)
                 s.stable = torch.zeros(m, dtype=torch.int32, device=self.device)
+        if self.sync:
+            m = int(L.lib().fv_jpeg_sync_table_ints(L.i32(self.batch)))
+            assert m == self.batch * SYNC_JOB_INTS
+            self.sync_records = self.stream_bytes // self.subseq_bytes + self.batch      # a scan's last subsequence may be short
+            self._sync_scratch = torch.zeros(self.sync_records * SYNC_REC_BYTES // 4, dtype=torch.int32, device=self.device)
+            for s in self._slots:
+                s.sync_pin = torch.zeros(m, dtype=torch.int32).pin_memory()
+                s.sjobs = s.sync_pin.numpy().reshape(self.batch, SYNC_JOB_INTS)
+                s.sync = torch.zeros(m, dtype=torch.int32, device=self.device)
+                s.rused, s.sfallbacks = 0, 0
 
     def _filling(self):
         fresh = not self._open
@@ -347,6 +432,9 @@ class JpegImageStage(ImageStage):
             s.jtop, s.sused, s.lanes = getattr(self, "coef_elems", 0), 0, 0      # indexed samples reserve from the top down
             if self.stream_bytes:
                 s.srecords[:] = 0
+            if self.sync:
+                s.sjobs[:] = 0
+                s.rused, s.sfallbacks = 0, 0
         return s
 
     def put(self, i, array_hwc_u8, crop=None, out_full=None, window=(0, 0), flip=False):
@@ -490,6 +578,85 @@ class JpegImageStage(ImageStage):
             rec[19:23] = (t, l, h, w)
             rec.view(np.uint32)[23:25] = (off & 0xffffffff, off >> 32)
 
+    def put_jpeg_sync(self, i, data, crop=None, out_full=None, window=(0, 0), flip=False):
+        """``put_jpeg_indexed`` of a file WITHOUT an index: the same meaning, argument checks and PIL fallback outside the
+        resampler's range, and no Huffman code is decoded here.  The markers are parsed, and the tables, a reserved entry
+        region for the groups the crop's MCU window meets and the whole scan are copied into the pinned stream pool (one
+        foreign call) with the dense record, the stream record and the sync job; ``fv_jpeg_sync`` writes the entries on
+        the device and ``fv_jpeg_huff`` the coefficients.  A file the stage function refuses -- unserved, a restart
+        interval, separate chroma tables, fill bytes inside the scan, a scan above ``max_scan_bytes`` -- goes through
+        ``put_jpeg`` inside this call and is counted in ``last_sync_fallbacks``: one call for any ``.jpg``.
+
+        NOT caught here: a file whose markers parse but whose scan is damaged or cut short (a stray RSTn without a restart
+        interval, missing bytes).  ``put_jpeg`` decodes on the host and would fall back to PIL or raise for it; this call
+        decodes nothing, so the damage shows only on the device: ``fv_jpeg_sync`` gives the sample status 6 and writes no
+        entry, its coefficients and pixels in the batch are unspecified, and nothing raises -- ``stream_status()``, which
+        synchronises, is the only place it is visible.  A loader that cannot vouch for its files checks ``stream_status()``
+        per batch or keeps ``put_jpeg`` for them."""
+        if not self.sync:
+            raise RuntimeError("JpegImageStage.put_jpeg_sync: the stage was built without sync=True")
+        i, data = int(i), _as_bytes(data)
+        H, W, _, cls, ok, _, _, _ = _probe(data)
+        if not ok:
+            return self._put_sync_refused(i, data, crop, out_full, window, flip)
+        t, l, h, w = (0, 0, H, W) if crop is None else (int(v) for v in crop)
+        if min(t, l) < 0 or h < 1 or w < 1 or t + h > H or l + w > W:
+            raise ValueError(f"ImageStage.put: crop {tuple(crop)} of sample {i} does not lie inside its {H}x{W} image")
+        o_h, o_w = (self.s_h, self.s_w) if out_full is None else _pair(out_full)
+        win_y, win_x = (int(v) for v in window)
+        if o_h < 1 or o_w < 1 or win_y < 0 or win_x < 0 or win_y + self.s_h > o_h or win_x + self.s_w > o_w:
+            raise ValueError(f"ImageStage.put: the {self.s_h}x{self.s_w} window at {(win_y, win_x)} of sample {i} does not lie "
+                             f"inside its {o_h}x{o_w} resize")
+        if not resample_ok(self.batch, self.s_h, self.s_w, h, w, o_h, o_w, win_y, win_x):
+            return self._put_decoded(i, data, crop, out_full, window, flip)      # ``put`` resizes it with PIL on the host
+        mcus = mcu_window(H, W, cls, (t, l, h, w))
+        n = window_elements(cls, mcus)
+        S = self.segment_mcus
+        lanes = ((mcus[0] + mcus[2] - 1) // S - mcus[0] // S + 1) * mcus[3]
+        with self._lock:
+            s = self._filling()
+            if not 0 <= i < self.batch:
+                raise IndexError(f"ImageStage.put: sample {i} of a batch of {self.batch}")
+            if s.host.filled[i]:
+                raise ValueError(f"ImageStage.put: sample {i} was already put in this batch")
+            if s.jtop - n < s.jused:
+                raise ValueError(f"JpegImageStage.put_jpeg_sync: sample {i} ({2 * n} coefficient bytes below offset {2 * s.jtop}) "
+                                 f"overflows coef_capacity_bytes = {2 * self.coef_elems}")
+            if self.segment_capacity and s.lanes + lanes > self.segment_capacity:
+                raise ValueError(f"JpegImageStage.put_jpeg_sync: sample {i} ({lanes} groups after {s.lanes}) overflows "
+                                 f"segment_capacity = {self.segment_capacity}")
+            at = (s.host.used + ALIGN - 1) // ALIGN * ALIGN            # ``reserve``'s own check, before anything is written
+            if at + h * w * 3 > self.capacity:
+                raise ValueError(f"ImageStage.put: sample {i} ({h * w * 3} bytes at offset {at}) overflows capacity_bytes = "
+                                 f"{self.capacity}")
+            rec, srec, job = s.records[i], s.srecords[i], s.sjobs[i]
+            used, rused = ctypes.c_longlong(s.sused), ctypes.c_longlong(s.rused)
+            rc = L.host_lib().fv_jpeg_sync_stage(ctypes.c_char_p(data), ctypes.c_longlong(len(data)), (ctypes.c_int * 4)(*mcus),
+                                                 L.i32(S), L.i32(self.subseq_bytes), ctypes.c_longlong(self.max_scan_bytes),
+                                                 ctypes.c_void_p(s.stream_pin.data_ptr()), ctypes.c_longlong(self.stream_bytes),
+                                                 ctypes.byref(used), ctypes.c_longlong(self.sync_records), ctypes.byref(rused),
+                                                 ctypes.c_longlong(s.jtop - n), ctypes.c_void_p(rec.ctypes.data),
+                                                 ctypes.c_void_p(srec.ctypes.data), ctypes.c_void_p(job.ctypes.data))
+            if rc == 0:
+                off = s.host.reserve(i, h, w, o_h, o_w, win_y, win_x, flip)
+                s.jtop, s.sused, s.rused, s.lanes = s.jtop - n, used.value, rused.value, s.lanes + lanes
+                rec[19:23] = (t, l, h, w)
+                rec.view(np.uint32)[23:25] = (off & 0xffffffff, off >> 32)
+                return
+            rec[:] = 0
+            srec[:] = 0
+            job[:] = 0
+            if rc not in SYNC_REFUSALS:
+                what = "stream_capacity_bytes" if rc == -15 else "the file"
+                raise ValueError(f"JpegImageStage.put_jpeg_sync: sample {i}: {INDEX_ERRORS.get(rc, ERRORS.get(rc, 'error'))} "
+                                 f"(code {rc}; {what})")
+        return self._put_sync_refused(i, data, crop, out_full, window, flip)
+
+    def _put_sync_refused(self, i, data, crop, out_full, window, flip):
+        with self._lock:
+            self.put_jpeg(i, data, crop=crop, out_full=out_full, window=window, flip=flip)
+            self._slots[self._fill].sfallbacks += 1
+
     def _put_packed(self, i, data, cls, mcus, blocks, crop, out_full, window, flip):
         """``put_jpeg`` of the packed form: decode into this thread's scratch, reserve the exact size, copy."""
         bound = 142 * blocks                                           # fv_jpeg_packed_bound
@@ -572,6 +739,9 @@ class JpegImageStage(ImageStage):
                 s.stream[:s.sused].copy_(s.stream_pin[:s.sused], non_blocking=True)
                 s.stable.copy_(s.stable_pin, non_blocking=True)
                 self.staged_stream_bytes = s.sused
+            if self.sync:
+                s.sync.copy_(s.sync_pin, non_blocking=True)
+                self.last_sync_fallbacks = s.sfallbacks
             self.last_jpeg_fallbacks = s.jfallbacks
             self.staged_coef_bytes = s.jused if self.coef_format == "packed" else 2 * s.jused
             super().commit()
@@ -589,6 +759,9 @@ class JpegImageStage(ImageStage):
                                             ne, b, st), "fv_jpeg_idct_packed")
         else:
             ne = ctypes.c_longlong(self.coef_elems)
+            if self.sync:
+                L.check(lib.fv_jpeg_sync(L.ptr(s.stream), ctypes.c_longlong(self.stream_bytes), L.ptr(s.sync), L.ptr(self._sync_scratch),
+                                         ctypes.c_longlong(self.sync_records * SYNC_REC_BYTES), b, st), "fv_jpeg_sync")
             if self.stream_bytes:
                 L.check(lib.fv_jpeg_huff(L.ptr(s.stream), ctypes.c_longlong(self.stream_bytes), L.ptr(s.stable), L.ptr(s.coef), ne, b, st),
                         "fv_jpeg_huff")
@@ -604,7 +777,22 @@ class JpegImageStage(ImageStage):
         s = self._ready
         if s is None or not self.stream_bytes:
             raise RuntimeError("JpegImageStage.stream_status: no indexed batch was committed")
-        return s.stable[:self.batch * SREC_INTS].view(self.batch, SREC_INTS)[:, 24].cpu()
+        huff = s.stable[:self.batch * SREC_INTS].view(self.batch, SREC_INTS)[:, 24].cpu()
+        if not self.sync:
+            return huff
+        # a sample fv_jpeg_sync gave up on (5: a job that does not fit, 6: the states turn invalid before the last group
+        # start needed) reports that, not the FV_JPEG_ST_RECORD its unwritten entries then give fv_jpeg_huff's lanes
+        sync = s.sync.view(self.batch, SYNC_JOB_INTS)[:, 24].cpu()
+        return torch.where(sync != 0, sync, huff)
+
+    def sync_rounds(self):
+        """The rounds of the fixed point that changed a state, per sample of the slot committed last, as ``fv_jpeg_sync``
+        left them: (batch,) int32 on the host, 0 for a sample without a sync job.  A diagnostic: it synchronises, and
+        ``resample`` never calls it."""
+        s = self._ready
+        if s is None or not self.sync:
+            raise RuntimeError("JpegImageStage.sync_rounds: no batch of a sync=True stage was committed")
+        return s.sync.view(self.batch, SYNC_JOB_INTS)[:, 25].cpu()
 
     def region(self, i):
         """The (h, w, 3) uint8 device view of sample ``i``'s source rectangle in the pool of the slot committed last."""

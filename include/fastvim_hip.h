@@ -96,7 +96,10 @@ const char* fv_last_error(void);
  *      fv_jpeg_huff were ADDED (device-side Huffman decoding from a per-file index: THE INDEX below); no existing entry
  *      point, record layout or default changed.
  *      Later, still 3: fv_cellaug_geom and fv_cellaug_filter were ADDED (the cell-image augmentation of the channel
- *      models' loader on planar uint8 planes: THE CELL RECORD below); no existing entry point changed. */
+ *      models' loader on planar uint8 planes: THE CELL RECORD below); no existing entry point changed.
+ *      Later, still 3: fv_jpeg_sync_stage, fv_jpeg_sync_host, fv_jpeg_sync_table_ints and fv_jpeg_sync were ADDED (the
+ *      entries fv_jpeg_huff starts from, found on the device without a sidecar index: ENTRIES MADE ON THE DEVICE below);
+ *      no existing entry point, record layout or default changed. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -1337,6 +1340,55 @@ int fv_randaug_apply(const void* in, void* out, const int* plan, const void* ws,
  *   range; beyond it and from a marker on the reader delivers zero bits), every store against coef_elems, and every loop
  *   is bounded independently of the stream: a corrupt stream or index gives unspecified coefficients and a non-zero
  *   status word ([24], a plain store), never a hang or an access out of range.  stream_pool and coef 16-byte aligned.
+ *
+ * ENTRIES MADE ON THE DEVICE (opt-in; nothing above changes).  A file without a sidecar index: the device finds the group
+ * starts itself.  A baseline Huffman stream re-synchronises -- a decoder started at a wrong bit soon falls into step with
+ * the true one -- so the scan is cut into SUBSEQUENCES of `subseq_bytes` bytes of the file (a boundary that falls on a
+ * stuffed 0x00 lies one byte later), each is decoded from its first bit with (block 0, a DC code next), and then again
+ * from its predecessor's exit state until a round changes nothing; an INVALID exit state -- a speculative decode that met a
+ * bad code or a run past 63 -- is not handed on, its successor keeps its own state meanwhile.  Subsequence 0 starts from the scan's true start, so
+ * after round i subsequence i is right: the fixed point is the serial decoder's, whether or not the stream synchronised.
+ * A prefix sum over the subsequences' MCU counts and DC sums gives every MCU start its number and predictors, and the
+ * starts the window needs are written as ENTRIES of THE INDEX, where fv_jpeg_huff reads them.  csrc/jpeg_sync_core.h is the
+ * decoder, one text for host and device.  Served: what fv_jpeg_build_index serves.
+ * fv_jpeg_sync_stage(data, nbytes, window, segment_mcus, subseq_bytes, max_scan_bytes, pool, pool_capacity_bytes, pool_used,
+ *   scratch_capacity_records, scratch_used, coef_base, record, stream_record, job): host, no state, no Huffman code
+ *   decoded.  Parses the markers; refuses what fv_jpeg_build_index refuses -- FV_JPEG_E_UNSERVED with job[0] = 0 and the
+ *   FV_JPEG_R_* reason in job[1] (restart intervals and separate chroma table pairs among them), FV_JPEG_E_TRUNCATED for
+ *   fill bytes inside the scan and for an empty scan -- FV_JPEG_E_WINDOW, and a scan (from the first entropy-coded byte to
+ *   the first 0xFF that no 0x00 follows) of more than min(max_scan_bytes, 2^26) bytes: FV_JPEG_E_SCAN_SIZE.  subseq_bytes:
+ *   a power of two in [16, 1024] (a symbol is at most 31 bits: 16 bytes always hold a symbol start); segment_mcus as S
+ *   above.  Appends to the host stream pool from the next multiple of 16 at or above *pool_used: the four tables, a
+ *   RESERVED region of 16 bytes per group that meets the window, filled with 0xFF -- an entry nobody wrote has bit > 7,
+ *   and fv_jpeg_huff's lane returns FV_JPEG_ST_RECORD for it -- and the whole scan, zero-padded to 16; takes
+ *   ceil(scan bytes / subseq_bytes) records of the scratch buffer from *scratch_used on -- at most FV_JPEG_SYNC_MAX_SUBSEQS,
+ *   a longer scan is FV_JPEG_E_SCAN_SIZE too: the cap bounds the rounds of a launch.  FV_JPEG_E_CAPACITY if either does
+ *   not fit: then nothing is written and the counters stay; on success both counters are advanced.  Writes the dense record and the stream record
+ *   fv_jpeg_index_stage writes ([22] the scan's bytes, [23] its offset in the file), and the SYNC JOB,
+ *   FV_JPEG_SYNC_JOB_INTS int32:
+ *     [0]        1: a job (0: none)        [1] sampling class        [2..5] the window: x0, y0, w, h in MCUs
+ *     [6]        MCUs per row of the image [7] S                     [8] [9] first group column the window meets, how many
+ *     [10] [11]  byte offset of the scan in the stream pool, low and high       [12] its bytes      [13] its offset in the file
+ *     [14]       the bit of the first byte the scan starts at (0)     [15] subseq_bytes      [16] subsequences
+ *     [17] [18]  byte offset of the entry region in the stream pool, [19] [20] of the tables
+ *     [21] [22]  the first scratch record of the job                  [23] MCU rows of the image
+ *     [24]       DEVICE: the status -- 0, FV_JPEG_ST_SYNC_JOB (a job that does not fit its buffers: nothing was read) or
+ *                FV_JPEG_ST_SYNC_LOST (the MCU starts in front of the first exit state that stays INVALID -- a bad code, a run
+ *                past 63, the end of the data -- do not reach the last group start the window needs: no entry was written)
+ *     [25]       DEVICE: the rounds that changed a state
+ *     [26..28]   fv_jpeg_sync_host ONLY (the device leaves them 0), what speculation was worth, over all subsequences but
+ *                the last: speculative exit states that were INVALID where the final one is not, those that were valid but
+ *                not the final one, and the longest run of the former          [29..31] 0
+ * fv_jpeg_sync_table_ints(batch): the words of the SYNC TABLE in device memory: `batch` sync jobs.
+ * fv_jpeg_sync(stream_pool, stream_bytes, sync_table, scratch, scratch_bytes, batch, stream): in front of fv_jpeg_huff.
+ *   One workgroup per sample, a grid of `batch`; a slot without a job returns at once.  `scratch`: FV_JPEG_SYNC_REC_BYTES
+ *   per subsequence, contents unspecified before and after.  Writes the entries of the groups the window needs into the
+ *   reserved region of the stream pool, each by exactly one lane, and words [24] [25] of the job.  Every job word is
+ *   checked against stream_bytes and scratch_bytes, every stream read against the staged scan, every loop is bounded by
+ *   the job's byte and subsequence counts; plain stores, no atomics: a corrupt stream gives a status, or entries that are
+ *   the serial decoder's up to the damage, never a hang or an access out of range.  stream_pool and scratch 16-byte aligned.
+ * fv_jpeg_sync_host(pool, pool_bytes, job, scratch, scratch_records): host; the same passes and rounds over one job, one
+ *   subsequence after the other, on the HOST stream pool: fills the entry region and words [24] [25] as the device does.
  * ---------------------------------------------------------------------- */
 #define FV_JPEG_INFO_INTS 8
 #define FV_JPEG_REC_INTS 224
@@ -1396,6 +1448,20 @@ int fv_jpeg_index_stage(const void* data, long long nbytes, const void* index, l
 long long fv_jpeg_stream_table_ints(int batch);
 int fv_jpeg_huff(const void* stream_pool, long long stream_bytes, int* stream_table, void* coef, long long coef_elems,
                  int batch, fv_stream_t stream);
+#define FV_JPEG_SYNC_JOB_INTS 32
+#define FV_JPEG_SYNC_REC_BYTES 32
+#define FV_JPEG_SYNC_MAX_SUBSEQS 16384
+#define FV_JPEG_E_SCAN_SIZE (-20)
+#define FV_JPEG_ST_SYNC_JOB 5
+#define FV_JPEG_ST_SYNC_LOST 6
+int fv_jpeg_sync_stage(const void* data, long long nbytes, const int* window, int segment_mcus, int subseq_bytes,
+                       long long max_scan_bytes, void* pool, long long pool_capacity_bytes, long long* pool_used,
+                       long long scratch_capacity_records, long long* scratch_used, long long coef_base, int* record,
+                       int* stream_record, int* job);
+int fv_jpeg_sync_host(void* pool, long long pool_bytes, int* job, void* scratch, long long scratch_records);
+long long fv_jpeg_sync_table_ints(int batch);
+int fv_jpeg_sync(void* stream_pool, long long stream_bytes, int* sync_table, void* scratch, long long scratch_bytes, int batch,
+                 fv_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Device-side cell-image augmentation: the pixel work of the reference's CellAugmentation(is_train=True)
