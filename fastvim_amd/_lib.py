@@ -50,6 +50,7 @@ C_ABI_SYMBOLS = (
     "fv_jpeg_index_bound", "fv_jpeg_build_index", "fv_jpeg_index_stage", "fv_jpeg_stream_table_ints", "fv_jpeg_huff",
     "fv_cellaug_geom", "fv_cellaug_filter",
     "fv_jpeg_sync_stage", "fv_jpeg_sync_host", "fv_jpeg_sync_table_ints", "fv_jpeg_sync",
+    "fv_gemm_bf16_plan", "fv_gemm_bf16_tn_grouped_plan",
 )
 
 

@@ -982,17 +982,21 @@ int launch_k(const GemmParams& p, int splits, hipStream_t st) {
   return FV_OK;
 }
 
-template <int AMODE, int BMODE, int WM, int WN>
-int launch(const GemmParams& p, int splits, hipStream_t st) {
-  // LDS-DMA staging needs whole 64-deep K tiles in every split and >= 8 columns in K-slow operands
+// LDS-DMA staging of the 128 x 128 (and, in tuning builds, 256 x 64) tiles: it needs whole 64-deep K tiles in every split
+// and >= 8 columns in K-slow operands
+static bool plan_lds_dma(int amode, int bmode, int M, int N, int K, int k_per_split) {
   static const bool allow = (fv_tune("FASTVIM_GEMM_GLDS", 1) != 0);   // tuning hook
   // (measured: forward and data-gradient GEMMs -8..-20 %; the K-slow x K-slow weight-gradient form lost 10 % while its
   //  transposing reads were compiler-visible -- every K step waited for all LDS-DMA loads -- and gains 15 % with the
   //  opaque immediate-offset reads of KsFrags)
   static const bool ks_glds = (fv_tune("FASTVIM_WGRAD_GLDS", 1) != 0);   // tuning hook
-  const bool whole = (AMODE == KC || (ks_glds && p.M >= 8)) && p.K % BK == 0 && p.k_per_split % BK == 0 &&
-                     (BMODE == KC || p.N >= 8);
-  if (allow && whole) return launch_k<AMODE, BMODE, WM, WN, true>(p, splits, st);
+  const bool whole = (amode == KC || (ks_glds && M >= 8)) && K % BK == 0 && k_per_split % BK == 0 && (bmode == KC || N >= 8);
+  return allow && whole;
+}
+
+template <int AMODE, int BMODE, int WM, int WN>
+int launch(const GemmParams& p, int splits, bool lds_dma, hipStream_t st) {
+  if (lds_dma) return launch_k<AMODE, BMODE, WM, WN, true>(p, splits, st);
   return launch_k<AMODE, BMODE, WM, WN, false>(p, splits, st);
 }
 
@@ -1193,8 +1197,19 @@ int launch_stream(const GemmParams& p, hipStream_t st) {
   return FV_OK;
 }
 
-template <int AMODE, int BMODE>
-int launch_shape(const GemmParams& p, int splits, hipStream_t st) {
+// The launch of one fv_gemm_bf16 call, decided ONCE: gemm_plan() holds every rule, launch_shape() below launches what it
+// answers, and the C ABI's fv_gemm_bf16_plan reports the same answer (tests assert the kernel they mean before they run
+// it).  kind is one of FV_GEMM_KIND_* (include/fastvim_hip.h); a tuning build's extra tile shapes answer 100 + their hook value.
+struct GemmPlan {
+  int kind;
+  int tile_m, tile_n;
+  int lds_dma;      // operands staged global -> LDS by DMA (else through registers)
+  int grid;         // workgroups of the phased forms
+};
+enum { PK_TUNE_TALL = 100, PK_TUNE_256x64 = 141 };
+
+// p: M, N, K, k_per_split, c_fp32, bias (null or not) and ldc are read -- no pointer is followed
+static GemmPlan gemm_plan(int AMODE, int BMODE, const GemmParams& p, int splits, int cus) {
   // N a multiple of 192 (FastVim-T/S/B: d, 2*d_in): 128x192 tiles, the A panel is read N/192 times instead of
   // N/128.  Measured on MI355X: N = 384 -9 %, FastVim-S/B steps -3 %; N = 192 neutral (K-contiguous B) or +12 %
   // (K-slow B, 4-way swizzle), N = 768 with K = 192 +3 % -- those keep the 128-wide tiles.
@@ -1204,23 +1219,23 @@ int launch_shape(const GemmParams& p, int splits, hipStream_t st) {
   // sizes it was measured on (HBM-cold, M = 25088: in_proj forward 24.3 -> 23.0 us, in_proj data gradient
   // 20.4 -> 18.3; whole step 7.635 -> 7.59 ms)
   static const bool stream = (fv_tune("FASTVIM_GEMM_STREAM", 1) != 0);   // tuning hook
-  if constexpr (AMODE == KC) {
+  if (AMODE == KC) {
     // (K-slow B only: inside the training step, where A was written by the previous kernel, the <KC, KC> forward
     //  GEMMs measured 21.1 -> 22.4 ms per 27 steps with it, the <KC, KS> data gradients 23.8 -> 20.1 ms)
     if (stream && BMODE == KS && !tall && whole_k && splits == 1 && !p.c_fp32 && p.M >= 8192 && p.K >= 128 &&
         p.N % 192 == 0 && (long)p.N * p.K <= 192 * 768)
-      return launch_stream<BMODE, 2, 4, 3, 4, 3>(p, st);
+      return GemmPlan{FV_GEMM_KIND_STREAM, 128, 192, 1, 0};
   }
 #ifdef FASTVIM_TUNING_HOOKS      // tile-shape experiments that lost their A/B: tuning builds only
   if (tall && p.M >= 256 && p.N >= 128 && (AMODE != KC || whole_k)) {
-    constexpr bool G = AMODE == KC;
-    if (tall == 1) return launch_k<AMODE, BMODE, 2, 2, G, 4, 8>(p, splits, st);
-    if (tall == 2 && p.N % 192 == 0) return launch_k<AMODE, BMODE, 2, 2, G, 6, 8>(p, splits, st);
-    if (tall == 3) return launch_k<AMODE, BMODE, 2, 2, G, 8, 8>(p, splits, st);
-    if (tall == 4) return launch_k<AMODE, BMODE, 4, 2, G, 8, 4>(p, splits, st);     // 8 waves of 64x128: 256x256
-    if (tall == 5) return launch_k<AMODE, BMODE, 2, 4, G, 4, 8>(p, splits, st);     // 8 waves of 128x64: 256x256
-    if (tall == 6) return launch_k<AMODE, BMODE, 4, 2, G, 4, 4>(p, splits, st);     // 8 waves of 64x64: 256x128
-    if (tall == 7 && p.N % 192 == 0) return launch_k<AMODE, BMODE, 4, 2, G, 6, 4>(p, splits, st);   // 8 waves of 64x96: 256x192
+    const int G = AMODE == KC;
+    if (tall == 1) return GemmPlan{PK_TUNE_TALL + 1, 256, 128, G, 0};
+    if (tall == 2 && p.N % 192 == 0) return GemmPlan{PK_TUNE_TALL + 2, 256, 192, G, 0};
+    if (tall == 3) return GemmPlan{PK_TUNE_TALL + 3, 256, 256, G, 0};
+    if (tall == 4) return GemmPlan{PK_TUNE_TALL + 4, 256, 256, G, 0};     // 8 waves of 64x128
+    if (tall == 5) return GemmPlan{PK_TUNE_TALL + 5, 256, 256, G, 0};     // 8 waves of 128x64
+    if (tall == 6) return GemmPlan{PK_TUNE_TALL + 6, 256, 128, G, 0};     // 8 waves of 64x64
+    if (tall == 7 && p.N % 192 == 0) return GemmPlan{PK_TUNE_TALL + 7, 256, 192, G, 0};   // 8 waves of 64x96
   }
 #endif
   // phased 256 x 256 kernel (gemm_nt256p_kernel): one workgroup per CU, so it wants whole rounds of 256 tiles -- from
@@ -1234,36 +1249,20 @@ int launch_shape(const GemmParams& p, int splits, hipStream_t st) {
   // (short K loops lose: K = 128 / 192 forward +2-8 %, K = 384 data gradient even, K = 192 data gradient +8 %)
   if ((phased & (BMODE == KC ? 1 : 2)) && AMODE == KC && p.N % 256 == 0 && p.K % BK == 0 && p.K >= (BMODE == KC ? 384 : 512) && splits == 1 &&
       !p.c_fp32 && !p.bias && p.ldc % 8 == 0 && (long)fv_cdiv(p.M, 256) * (p.N / 256) >= p256_min) {
-    static FvOncePerDevice attr;   
-    if (attr.first()) {
-      (void)hipFuncSetAttribute((const void*)gemm_nt256p_kernel<BMODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-      (void)0;     
-    }
-    GemmParams q = p;
-    q.rb_period = fv_tune("FASTVIM_GEMM_P256_DBG", 0);      // phase probe (tuning builds)
     // persistent workgroups, one per CU (round 3): the next tile's first K tiles are requested before a tile's C leaves.
     // Same C bit for bit; same box: FastVim-B 224 px 29.04 -> 28.75 ms per step, 2048 px 109.5 -> 107.9, FastChannelVim-S
     // 44.48 -> 44.30; stand-alone 2-5 % per GEMM (profiles/r03_p256_persistent.log)
     static const int persist = fv_tune("FASTVIM_GEMM_P256_PERSIST", 1);   // tuning hook: 0 = one workgroup per tile
     const int ntile = fv_cdiv(p.M, 256) * (p.N / 256);
-    const int cus8 = fv_cu_count() / 8 * 8;
-    static FvOncePerDevice attr2;
-    if (attr2.first())
-      (void)hipFuncSetAttribute((const void*)gemm_nt256pp_kernel<BMODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (persist && cus8 >= 8 && ntile > cus8) {
-      hipLaunchKernelGGL(gemm_nt256pp_kernel<BMODE>, dim3(cus8), dim3(512), 160 * 1024, st, q);
-      FV_LAUNCH_CHECK();
-      return FV_OK;
-    }
-    hipLaunchKernelGGL(gemm_nt256p_kernel<BMODE>, dim3(ntile), dim3(512), 128 * 1024, st, q);
-    FV_LAUNCH_CHECK();
-    return FV_OK;
+    const int cus8 = cus / 8 * 8;
+    if (persist && cus8 >= 8 && ntile > cus8) return GemmPlan{FV_GEMM_KIND_PHASED_PERSISTENT, 256, 256, 1, cus8};
+    return GemmPlan{FV_GEMM_KIND_PHASED_TILE, 256, 256, 1, ntile};
   }
   // FastVim-B in_proj forward (N = 3072, K = 768): eight waves of 128x64 on a 256x256 tile, -10 % (161 -> 144 us);
   // measured slower at every FastVim-T/S shape and for the data-gradient forms, which keep the 4-wave tiles
   static const bool big = (fv_tune("FASTVIM_GEMM_BIG", 1) != 0);   // tuning hook
   if (big && !tall && AMODE == KC && BMODE == KC && p.N % 256 == 0 && p.N >= 2048 && p.K >= 512 && p.M >= 4096 && whole_k)
-    return launch_k<AMODE, BMODE, 2, 4, true, 4, 8>(p, splits, st);
+    return GemmPlan{FV_GEMM_KIND_WAVE8_256, 256, 256, 1, 0};
   // 160 x 128 tiles where they save rounds of workgroups: the per-tile launches run in rounds of 512 resident workgroups
   // (two per CU), so a launch costs about rounds x tile area.  FastVim-T in_proj forward (M = 25 088, N = 768, K = 192):
   // 1 176 tiles of 128 x 128 = 2.3 -> 3 rounds, 942 tiles of 160 x 128 = 1.84 -> 2 rounds at 1.25 x the area: 3.0 -> 2.5
@@ -1273,34 +1272,102 @@ int launch_shape(const GemmParams& p, int splits, hipStream_t st) {
   // in_proj data gradient (N = 768, K = 3072) 3.0 -> 2.5, the channel model's (M = 100 352) 6.0 -> 5.0 / 10.5 -> 10.0
   static const int m160 = fv_tune("FASTVIM_GEMM_M160", 1);   // tuning hook
   if (m160 && !tall && AMODE == KC && whole_k && splits == 1 && p.N % 128 == 0 && p.M >= 4096) {
-    const long slots = 2L * fv_cu_count();
+    const long slots = 2L * cus;
     auto cost = [&](long bm, long bn) { return fv_cdiv((long)fv_cdiv(p.M, bm) * (p.N / bn), slots) * bm * bn; };
     const bool wide_ok = p.N % 192 == 0 && p.N >= 384 && !(p.N == 768 && p.K <= 192);
     const bool n96_ok = p.N % 96 == 0 && p.N < 384;
     // against the shape that would run otherwise (128 x 192 where the width allows it), with 8 % in hand for the taller
     // tile's larger L2 -> LDS fill per flop
     const long cur = wide_ok ? cost(128, 192) : cost(128, 128);
-    if (!n96_ok && cost(160, 128) * 27 / 25 < cur) return launch_k<AMODE, BMODE, 2, 2, true, 4, 5>(p, splits, st);
+    if (!n96_ok && cost(160, 128) * 27 / 25 < cur) return GemmPlan{FV_GEMM_KIND_160x128, 160, 128, 1, 0};
   }
   // N = 192 (FastVim-T: out_proj forward, in_proj data gradient, patch embed): two 96-wide tiles cover it exactly,
   // two 128-wide ones compute and load a quarter too much
   static const int n96 = fv_tune("FASTVIM_GEMM_N96", 1);   // tuning hook (out_proj forward 11.2 -> 10.1 us, in_proj dgrad 18.0 -> 16.9)
   if (n96 && !tall && AMODE == KC && p.N % 96 == 0 && p.N < 384 && whole_k)
-    return launch_k<AMODE, BMODE, 2, 2, true, 3>(p, splits, st);
+    return GemmPlan{FV_GEMM_KIND_128x96, 128, 96, 1, 0};
   static const bool wide = (fv_tune("FASTVIM_GEMM_N192", 1) != 0);   // tuning hook
   if (wide && AMODE == KC && p.N % 192 == 0 && p.N >= 384 && !(p.N == 768 && p.K <= 192) && p.K % BK == 0 &&
       p.k_per_split % BK == 0)
-    return launch_k<AMODE, BMODE, 2, 2, true, 6>(p, splits, st);
+    return GemmPlan{FV_GEMM_KIND_128x192, 128, 192, 1, 0};
   // 128x128 everywhere else: with LDS-DMA staging the 256x64 shape no longer pays at N = 192 (measured equal or
   // up to 8 % slower); it stays available for tuning
+  const int dma = plan_lds_dma(AMODE, BMODE, p.M, p.N, p.K, p.k_per_split);
 #ifdef FASTVIM_TUNING_HOOKS
   static const int force = fv_tune("FASTVIM_GEMM_TILE", 0);   // 41 = 256x64
-  if (force == 41 && p.M >= 256) return launch<AMODE, BMODE, 4, 1>(p, splits, st);
+  if (force == 41 && p.M >= 256) return GemmPlan{PK_TUNE_256x64, 256, 64, dma, 0};
 #endif
-  return launch<AMODE, BMODE, 2, 2>(p, splits, st);
+  return GemmPlan{FV_GEMM_KIND_128x128, 128, 128, dma, 0};
+}
+
+template <int AMODE, int BMODE>
+int launch_shape(const GemmParams& p, int splits, hipStream_t st) {
+  const GemmPlan pl = gemm_plan(AMODE, BMODE, p, splits, fv_cu_count());
+  switch (pl.kind) {
+    case FV_GEMM_KIND_STREAM:
+      if constexpr (AMODE == KC) return launch_stream<BMODE, 2, 4, 3, 4, 3>(p, st);
+      break;
+    case FV_GEMM_KIND_PHASED_TILE:
+    case FV_GEMM_KIND_PHASED_PERSISTENT:
+      if constexpr (AMODE == KC) {
+        static FvOncePerDevice attr, attr2;
+        if (attr.first())
+          (void)hipFuncSetAttribute((const void*)gemm_nt256p_kernel<BMODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        if (attr2.first())
+          (void)hipFuncSetAttribute((const void*)gemm_nt256pp_kernel<BMODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        GemmParams q = p;
+        q.rb_period = fv_tune("FASTVIM_GEMM_P256_DBG", 0);      // phase probe (tuning builds)
+        if (pl.kind == FV_GEMM_KIND_PHASED_PERSISTENT)
+          hipLaunchKernelGGL(gemm_nt256pp_kernel<BMODE>, dim3(pl.grid), dim3(512), 160 * 1024, st, q);
+        else
+          hipLaunchKernelGGL(gemm_nt256p_kernel<BMODE>, dim3(pl.grid), dim3(512), 128 * 1024, st, q);
+        FV_LAUNCH_CHECK();
+        return FV_OK;
+      }
+      break;
+    case FV_GEMM_KIND_WAVE8_256: return launch_k<AMODE, BMODE, 2, 4, true, 4, 8>(p, splits, st);
+    case FV_GEMM_KIND_160x128: return launch_k<AMODE, BMODE, 2, 2, true, 4, 5>(p, splits, st);
+    case FV_GEMM_KIND_128x96: return launch_k<AMODE, BMODE, 2, 2, true, 3>(p, splits, st);
+    case FV_GEMM_KIND_128x192: return launch_k<AMODE, BMODE, 2, 2, true, 6>(p, splits, st);
+    case FV_GEMM_KIND_128x128: return launch<AMODE, BMODE, 2, 2>(p, splits, pl.lds_dma != 0, st);
+#ifdef FASTVIM_TUNING_HOOKS
+    case PK_TUNE_TALL + 1: return launch_k<AMODE, BMODE, 2, 2, AMODE == KC, 4, 8>(p, splits, st);
+    case PK_TUNE_TALL + 2: return launch_k<AMODE, BMODE, 2, 2, AMODE == KC, 6, 8>(p, splits, st);
+    case PK_TUNE_TALL + 3: return launch_k<AMODE, BMODE, 2, 2, AMODE == KC, 8, 8>(p, splits, st);
+    case PK_TUNE_TALL + 4: return launch_k<AMODE, BMODE, 4, 2, AMODE == KC, 8, 4>(p, splits, st);
+    case PK_TUNE_TALL + 5: return launch_k<AMODE, BMODE, 2, 4, AMODE == KC, 4, 8>(p, splits, st);
+    case PK_TUNE_TALL + 6: return launch_k<AMODE, BMODE, 4, 2, AMODE == KC, 4, 4>(p, splits, st);
+    case PK_TUNE_TALL + 7: return launch_k<AMODE, BMODE, 4, 2, AMODE == KC, 6, 4>(p, splits, st);
+    case PK_TUNE_256x64: return launch<AMODE, BMODE, 4, 1>(p, splits, pl.lds_dma != 0, st);
+#endif
+    default: break;
+  }
+  fv_set_error("gemm_bf16: no launch for plan kind %d", pl.kind);
+  return FV_ERR_UNSUPPORTED;
 }
 
 }  // namespace
+
+// The checks of fv_gemm_bf16 that follow no pointer, and the extents, ldc and K range per split of p: shared by the entry
+// and by fv_gemm_bf16_plan, so that the query refuses exactly what the entry refuses on its shape.
+static int gemm_shape(GemmParams& p, int M, int N, int K, long ldc, int a_k_slow, int b_k_slow, int c_fp32, int splits) {
+  FV_CHECK(M > 0 && N > 0 && K > 0 && splits >= 1, "gemm_bf16: empty problem");
+  FV_CHECK(ldc % 4 == 0, "gemm_bf16: C must be 16-byte aligned with ldc %% 4 == 0");
+  FV_CHECK(splits == 1 || c_fp32, "gemm_bf16: split-K partials must be fp32");
+  FV_CHECK(a_k_slow ? M % 8 == 0 : K % 8 == 0, "gemm_bf16: A's contiguous extent must be a multiple of 8");
+  FV_CHECK(b_k_slow ? N % 8 == 0 : K % 8 == 0, "gemm_bf16: B's contiguous extent must be a multiple of 8");
+  p.M = M; p.N = N; p.K = K; p.ldc = ldc; p.c_fp32 = c_fp32;
+  const int kps = fv_cdiv(fv_cdiv(K, splits), BK) * BK;
+  p.k_per_split = kps;
+  p.c_split_stride = (long)M * ldc;
+  const int zs = fv_cdiv(K, kps);
+  FV_CHECK(zs == splits, "gemm_bf16: K=%d cannot be cut into %d slices of whole 64-deep tiles (got %d)", K, splits, zs);
+  if (a_k_slow && !b_k_slow) {
+    fv_set_error("gemm_bf16: A K-slow with B K-contiguous is not built");
+    return FV_ERR_UNSUPPORTED;
+  }
+  return FV_OK;
+}
 
 static int gemm_entry(const void* A, const void* B, void* C, const float* bias, int rb_period, int M, int N, int K,
                       long lda, long ldb, long ldc, int a_k_slow, int b_k_slow, int c_fp32, int splits,
@@ -1322,27 +1389,38 @@ static int gemm_entry(const void* A, const void* B, void* C, const float* bias, 
                       long lda, long ldb, long ldc, int a_k_slow, int b_k_slow, int c_fp32, int splits,
                       fv_stream_t stream) {
   FV_CHECK(A && B && C, "gemm_bf16: null pointer");
-  FV_CHECK(M > 0 && N > 0 && K > 0 && splits >= 1, "gemm_bf16: empty problem");
   FV_CHECK(lda % 8 == 0 && ldb % 8 == 0, "gemm_bf16: leading dimensions must be multiples of 8 (16-byte rows)");
   FV_CHECK(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0, "gemm_bf16: operands must be 16-byte aligned");
-  FV_CHECK(ldc % 4 == 0 && ((uintptr_t)C & 15) == 0, "gemm_bf16: C must be 16-byte aligned with ldc %% 4 == 0");
-  FV_CHECK(splits == 1 || c_fp32, "gemm_bf16: split-K partials must be fp32");
-  FV_CHECK(a_k_slow ? M % 8 == 0 : K % 8 == 0, "gemm_bf16: A's contiguous extent must be a multiple of 8");
-  FV_CHECK(b_k_slow ? N % 8 == 0 : K % 8 == 0, "gemm_bf16: B's contiguous extent must be a multiple of 8");
+  FV_CHECK(((uintptr_t)C & 15) == 0, "gemm_bf16: C must be 16-byte aligned with ldc %% 4 == 0");
   GemmParams p{};
+  const int rc = gemm_shape(p, M, N, K, ldc, a_k_slow, b_k_slow, c_fp32, splits);
+  if (rc != FV_OK) return rc;
   p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = C; p.bias = bias;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.c_fp32 = c_fp32; p.rb_period = rb_period;
-  int kps = fv_cdiv(fv_cdiv(K, splits), BK) * BK;
-  p.k_per_split = kps;
-  p.c_split_stride = (long)M * ldc;
-  const int zs = fv_cdiv(K, kps);
-  FV_CHECK(zs == splits, "gemm_bf16: K=%d cannot be cut into %d slices of whole 64-deep tiles (got %d)", K, splits, zs);
+  p.lda = lda; p.ldb = ldb; p.rb_period = rb_period;
   hipStream_t st = (hipStream_t)stream;
   if (!a_k_slow && !b_k_slow) return launch_shape<KC, KC>(p, splits, st);
   if (!a_k_slow && b_k_slow) return launch_shape<KC, KS>(p, splits, st);
-  if (a_k_slow && b_k_slow) return launch_shape<KS, KS>(p, splits, st);
-  fv_set_error("gemm_bf16: A K-slow with B K-contiguous is not built");
-  return FV_ERR_UNSUPPORTED;
+  return launch_shape<KS, KS>(p, splits, st);
+}
+
+// The launch fv_gemm_bf16 makes for these arguments (gemm_plan above, the function the launch itself asks), without
+// launching: cus = 0 asks for the current device's CU count, another value answers for a part with that many.
+extern "C" int fv_gemm_bf16_plan(int M, int N, int K, int a_k_slow, int b_k_slow, int c_fp32, int has_bias, int rb_period,
+                                 long ldc, int splits, int cus, int* tile_m, int* tile_n, int* lds_dma) {
+  FV_CHECK(cus >= 0, "gemm_bf16_plan: negative CU count");
+  FV_CHECK(rb_period <= 0 || (has_bias && c_fp32 && !a_k_slow && !b_k_slow && splits == 1),
+           "gemm_bf16_plan: a row-periodic bias table goes with fp32 C, K-contiguous operands and one K slice");
+  GemmParams p{};
+  const int rc = gemm_shape(p, M, N, K, ldc, a_k_slow, b_k_slow, c_fp32, splits);
+  if (rc != FV_OK) return rc;
+  static const float some_bias = 0.f;
+  p.bias = has_bias ? &some_bias : nullptr;      // the plan asks only whether there is one
+  p.rb_period = rb_period;
+  const GemmPlan pl = gemm_plan(a_k_slow ? KS : KC, b_k_slow ? KS : KC, p, splits, cus > 0 ? cus : fv_cu_count());
+  if (tile_m) *tile_m = pl.tile_m;
+  if (tile_n) *tile_n = pl.tile_n;
+  if (lds_dma) *lds_dma = pl.lds_dma;
+  return pl.kind;
 }
 
 // Rows per workgroup of the fused projection + norm kernels (64-row MFMA tiles, two workgroups resident per CU).  Dealing
@@ -1500,6 +1578,107 @@ extern "C" int fv_gemm_bf16_tn_grouped(const void* const* x, const void* const* 
   return fv_gemm_bf16_tn_grouped_ld(x, y, parts, Kd, M, N, nullptr, nullptr, splits, count, stream);
 }
 
+// ONE launch of the grouped entry, decided once: grouped_problem() checks and describes a problem without its pointers,
+// grouped_plan() holds every rule of the launch, the entry launches what it answers and fv_gemm_bf16_tn_grouped_plan
+// reports the same answer.
+struct GroupedPlan {
+  int cls;        // FV_GEMM_GROUPED_*: index of the tile shape below
+  int dma;        // operands staged by LDS-DMA (else through registers: class 0 only)
+  int phased;     // the phased 256 x 256 form (class 3 only)
+};
+static const int kGroupedTileM[6] = {128, 128, 192, 256, 256, 192}, kGroupedTileN[6] = {128, 192, 128, 256, 192, 256};
+
+// splits == -1: ONE K slice, ADDED to the (M, N) fp32 matrix parts points at (large outputs of the phased 256 x 256 form
+// only): no partial buffer, no reduction launch
+static int grouped_problem(GemmParams& p, int q, int Kd, int M, int N, int la, int lb, int splits) {
+  const bool direct = splits == -1;
+  const int nsl = direct ? 1 : splits;
+  FV_CHECK(Kd > 0 && M > 0 && N > 0 && nsl >= 1, "gemm_bf16_tn_grouped: bad problem %d", q);
+  FV_CHECK(la >= M && lb >= N && la % 8 == 0 && lb % 8 == 0 && N % 4 == 0,
+           "gemm_bf16_tn_grouped: problem %d: operands must be 16-byte aligned, row strides multiples of 8", q);
+  p.bias = nullptr;
+  p.M = M; p.N = N; p.K = Kd; p.lda = la; p.ldb = lb; p.ldc = N; p.c_fp32 = direct ? 2 : 1;
+  p.k_per_split = fv_cdiv(fv_cdiv(Kd, nsl), BK) * BK;
+  p.c_split_stride = (long)M * N;
+  FV_CHECK(fv_cdiv(Kd, p.k_per_split) == nsl,
+           "gemm_bf16_tn_grouped: problem %d: K=%d cannot be cut into %d slices of whole 64-deep tiles", q, Kd, nsl);
+  return FV_OK;
+}
+
+static int grouped_plan(const GemmParams* P, int n, GroupedPlan& out) {
+  bool any_direct = false;
+  for (int i = 0; i < n; ++i) any_direct = any_direct || P[i].c_fp32 == 2;
+  // LDS-DMA staging needs whole 64-deep K tiles in every slice and whole 16-byte column groups
+  static const bool ks_glds = (fv_tune("FASTVIM_WGRAD_GLDS", 1) != 0);   // tuning hook
+  bool dma = ks_glds;
+  for (int i = 0; i < n; ++i) {
+    const GemmParams& q = P[i];
+    dma = dma && q.K % BK == 0 && q.k_per_split % BK == 0 && ((q.M + 7) & ~7) <= q.lda && ((q.N + 7) & ~7) <= q.ldb &&
+          q.M >= 8 && q.N >= 8;
+  }
+  // Tile shape of the launch: the one that pads the problems least -- 128 x 192 for outputs 192 wide (in_proj at
+  // FastVim-T: 768 x 192), 192 x 128 for outputs 192 high (out_proj: 192 x 384), 128 x 128 otherwise and on ties.  A
+  // 128 x 128 tiling computes a quarter more than the output there and re-reads the operands from L2 2.8x / 2.3x;
+  // the launch is bound by L2 -> LDS traffic (phase probe: loads alone 194 us, multiply alone 133 us of 211).  The
+  // caller groups problems of one shape class per call (gemm.py).
+  static const int tile_env = fv_tune("FASTVIM_WGRAD_GROUP_TILE", 0);   // tuning hook: 1 = 128 x 128 always
+  long area[3] = {0, 0, 0};
+  for (int i = 0; i < n; ++i)
+    for (int c = 0; c < 3; ++c)
+      area[c] += (long)fv_cdiv(P[i].M, kGroupedTileM[c]) * kGroupedTileM[c] * fv_cdiv(P[i].N, kGroupedTileN[c]) * kGroupedTileN[c] *
+                 fv_cdiv(P[i].K, P[i].k_per_split);
+  int cls = 0;
+  if (dma && tile_env != 1) {
+    if (area[1] < area[cls]) cls = 1;
+    if (area[2] < area[cls]) cls = 2;
+  }
+  // 256 x 256 tiles on 8 waves when every output of the launch is a large multiple of them (FastVim-B: 3072 x 768 and
+  // 768 x 1536; gemm.py puts those in a launch of their own): half the L2 -> LDS traffic of 128 x 128, weight-gradient
+  // tail 5.6 -> 5.3 ms per FastVim-B step
+  bool big = dma && tile_env != 1;
+  for (int i = 0; i < n; ++i) big = big && P[i].M % 256 == 0 && P[i].N % 256 == 0 && (long)P[i].M * P[i].N >= 512 * 512;
+  if (big) {
+    static const int wg_phased = fv_tune("FASTVIM_WGRAD_P256", 1);   // tuning hook
+    bool two_tiles = true;             // the phased loop wants at least two K tiles per slice
+    for (int i = 0; i < n; ++i) two_tiles = two_tiles && P[i].k_per_split >= 2 * BK && P[i].K % P[i].k_per_split == 0;
+    FV_CHECK(!any_direct || (wg_phased && two_tiles), "gemm_bf16_tn_grouped: in-place accumulation (splits = -1) needs the phased 256 x 256 form");
+    out = GroupedPlan{FV_GEMM_GROUPED_256x256, 1, (wg_phased && two_tiles) ? 1 : 0};
+    return FV_OK;
+  }
+  FV_CHECK(!any_direct, "gemm_bf16_tn_grouped: in-place accumulation (splits = -1) is built for outputs that are multiples of 256 x 256 (>= 512 x 512) only");
+  // S-width outputs (d_model 384: in_proj 1536 x 384, out_proj 384 x 768 -- FastVim-S, FastChannelVim-S): 256 x 192 /
+  // 192 x 256 tiles on 8 waves, one workgroup per CU.  The launch is bound by the L2 -> LDS fill (see above): a 128 x 128
+  // tile moves 32 KB per 2.1 MFLOP of K step, these 56 KB per 6.3 -- 0.59 x the fill (gemm.py puts the two shapes in
+  // launches of their own)
+  // ONE rule decides (fv_gemm_bf16_tn_grouped_wide8: the host groups problems and picks split-K factors by it too --
+  // round 5 had the K threshold on the Python side only, so a launch Python had classed for 128 x 128 tiles could run
+  // on these with the wrong split factors)
+  bool c4 = dma && tile_env != 1, c5 = c4;
+  for (int i = 0; i < n; ++i) {
+    const int w8 = fv_gemm_bf16_tn_grouped_wide8(P[i].M, P[i].N, P[i].K);
+    c4 = c4 && w8 == FV_GEMM_GROUPED_256x192;
+    c5 = c5 && w8 == FV_GEMM_GROUPED_192x256;
+  }
+  if (c4 || c5) {
+    out = GroupedPlan{c4 ? FV_GEMM_GROUPED_256x192 : FV_GEMM_GROUPED_192x256, 1, 0};
+    return FV_OK;
+  }
+  // (256 x 192 tiles on 8 waves for the first class, half the L2 traffic again: 310 vs 316 us in the step in round 2 -- not
+  //  taken; again in round 3 with 6 / 8 / 12 / 14 K slices: step 5.73-5.84 against 5.68 ms, profiles/r03_ab_wgrad_t256_tiles.log)
+  out = GroupedPlan{cls, dma ? 1 : 0, 0};
+  return FV_OK;
+}
+
+template <int WM, int WN, bool GLDS, int NB, int MB>
+static void launch_grouped(const GroupedParams& G, int blocks, int xcd_order, hipStream_t st) {
+  constexpr size_t smem = (size_t)2 * (16 * MB * WM + 16 * NB * WN) * BK * 2;
+  static FvOncePerDevice attr;
+  if (smem > 64 * 1024 && attr.first())
+    (void)hipFuncSetAttribute((const void*)gemm_bf16_grouped_kernel<KS, KS, WM, WN, GLDS, NB, MB>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  hipLaunchKernelGGL((gemm_bf16_grouped_kernel<KS, KS, WM, WN, GLDS, NB, MB>), dim3(blocks), dim3(64 * WM * WN), smem, st, G, xcd_order);
+}
+
 extern "C" int fv_gemm_bf16_tn_grouped_ld(const void* const* x, const void* const* y, float* const* parts,
                                           const int* Kd, const int* M, const int* N, const int* ldx, const int* ldy,
                                           const int* splits, int count, fv_stream_t stream) {
@@ -1509,154 +1688,67 @@ extern "C" int fv_gemm_bf16_tn_grouped_ld(const void* const* x, const void* cons
   for (int base = 0; base < count; base += per_launch) {
     GroupedParams G{};
     const int n = count - base < per_launch ? count - base : per_launch;
-    bool any_direct = false;
     for (int i = 0; i < n; ++i) {
       const int q = base + i;
-      // splits[q] == -1: ONE K slice, ADDED to the (M, N) fp32 matrix parts[q] points at (large outputs of the phased
-      // 256 x 256 form only): no partial buffer, no reduction launch
-      const bool direct = splits[q] == -1;
-      const int nsl = direct ? 1 : splits[q];
-      any_direct = any_direct || direct;
-      FV_CHECK(x[q] && y[q] && parts[q] && Kd[q] > 0 && M[q] > 0 && N[q] > 0 && nsl >= 1,
-               "gemm_bf16_tn_grouped: bad problem %d", q);
-      const int la = ldx ? ldx[q] : M[q], lb = ldy ? ldy[q] : N[q];
-      FV_CHECK(la >= M[q] && lb >= N[q] && la % 8 == 0 && lb % 8 == 0 && ((uintptr_t)x[q] & 15) == 0 &&
-                   ((uintptr_t)y[q] & 15) == 0 && ((uintptr_t)parts[q] & 15) == 0 && N[q] % 4 == 0,
+      FV_CHECK(x[q] && y[q] && parts[q], "gemm_bf16_tn_grouped: bad problem %d", q);
+      FV_CHECK(((uintptr_t)x[q] & 15) == 0 && ((uintptr_t)y[q] & 15) == 0 && ((uintptr_t)parts[q] & 15) == 0,
                "gemm_bf16_tn_grouped: problem %d: operands must be 16-byte aligned, row strides multiples of 8", q);
       GemmParams& p = G.p[i];
-      p.A = (const bf16_t*)x[q]; p.B = (const bf16_t*)y[q]; p.C = parts[q]; p.bias = nullptr;
-      p.M = M[q]; p.N = N[q]; p.K = Kd[q]; p.lda = la; p.ldb = lb; p.ldc = N[q]; p.c_fp32 = direct ? 2 : 1;
-      p.k_per_split = fv_cdiv(fv_cdiv(Kd[q], nsl), BK) * BK;
-      p.c_split_stride = (long)M[q] * N[q];
-      FV_CHECK(fv_cdiv(Kd[q], p.k_per_split) == nsl,
-               "gemm_bf16_tn_grouped: problem %d: K=%d cannot be cut into %d slices of whole 64-deep tiles", q, Kd[q], nsl);
+      const int rc = grouped_problem(p, q, Kd[q], M[q], N[q], ldx ? ldx[q] : M[q], ldy ? ldy[q] : N[q], splits[q]);
+      if (rc != FV_OK) return rc;
+      p.A = (const bf16_t*)x[q]; p.B = (const bf16_t*)y[q]; p.C = parts[q];
     }
     G.count = n;
+    GroupedPlan pl{};
+    const int rc = grouped_plan(G.p, n, pl);
+    if (rc != FV_OK) return rc;
     static const int xcd_order = fv_tune("FASTVIM_WGRAD_GROUP_XCD", 1) | (fv_tune("FASTVIM_GEMM_DBG", 0) << 8);   // tuning hooks
-    // LDS-DMA staging needs whole 64-deep K tiles in every slice and whole 16-byte column groups
-    static const bool ks_glds = (fv_tune("FASTVIM_WGRAD_GLDS", 1) != 0);   // tuning hook
-    bool dma = ks_glds;
-    for (int i = 0; i < n; ++i) {
-      const GemmParams& q = G.p[i];
-      dma = dma && q.K % BK == 0 && q.k_per_split % BK == 0 && ((q.M + 7) & ~7) <= q.lda && ((q.N + 7) & ~7) <= q.ldb &&
-            q.M >= 8 && q.N >= 8;
-    }
-    // Tile shape of the launch: the one that pads the problems least -- 128 x 192 for outputs 192 wide (in_proj at
-    // FastVim-T: 768 x 192), 192 x 128 for outputs 192 high (out_proj: 192 x 384), 128 x 128 otherwise and on ties.  A
-    // 128 x 128 tiling computes a quarter more than the output there and re-reads the operands from L2 2.8x / 2.3x;
-    // the launch is bound by L2 -> LDS traffic (phase probe: loads alone 194 us, multiply alone 133 us of 211).  The
-    // caller groups problems of one shape class per call (gemm.py).
-    static const int tile_env = fv_tune("FASTVIM_WGRAD_GROUP_TILE", 0);   // tuning hook: 1 = 128 x 128 always
-    long area[3] = {0, 0, 0};
-    const int bm[3] = {128, 128, 192}, bn[3] = {128, 192, 128};
-    for (int i = 0; i < n; ++i)
-      for (int c = 0; c < 3; ++c)
-        area[c] += (long)fv_cdiv(G.p[i].M, bm[c]) * bm[c] * fv_cdiv(G.p[i].N, bn[c]) * bn[c] * fv_cdiv(G.p[i].K, G.p[i].k_per_split);
-    int cls = 0;
-    if (dma && tile_env != 1) {
-      if (area[1] < area[cls]) cls = 1;
-      if (area[2] < area[cls]) cls = 2;
-    }
-    // 256 x 256 tiles on 8 waves when every output of the launch is a large multiple of them (FastVim-B: 3072 x 768 and
-    // 768 x 1536; gemm.py puts those in a launch of their own): half the L2 -> LDS traffic of 128 x 128, weight-gradient
-    // tail 5.6 -> 5.3 ms per FastVim-B step
-    {
-      bool big = dma && tile_env != 1;
-      for (int i = 0; i < n; ++i)
-        big = big && G.p[i].M % 256 == 0 && G.p[i].N % 256 == 0 && (long)G.p[i].M * G.p[i].N >= 512 * 512;
-      if (big) {
-        int b2 = 0;
-        for (int i = 0; i < n; ++i) {
-          b2 += (G.p[i].M / 256) * (G.p[i].N / 256) * fv_cdiv(G.p[i].K, G.p[i].k_per_split);
-          G.blk_end[i] = b2;
-        }
-        static FvOncePerDevice attr;   
-        if (attr.first()) {
-          (void)hipFuncSetAttribute((const void*)gemm_bf16_grouped_kernel<KS, KS, 2, 4, true, 4, 8>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 256) * BK * 2);
-          (void)hipFuncSetAttribute((const void*)gemm_p256_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    2 * (256 + 256) * BK * 2);
-          (void)0;     
-        }
-        static const int wg_phased = fv_tune("FASTVIM_WGRAD_P256", 1);   // tuning hook
-        bool two_tiles = true;             // the phased loop wants at least two K tiles per slice
-        for (int i = 0; i < n; ++i) two_tiles = two_tiles && G.p[i].k_per_split >= 2 * BK && G.p[i].K % G.p[i].k_per_split == 0;
-        FV_CHECK(!any_direct || (wg_phased && two_tiles), "gemm_bf16_tn_grouped: in-place accumulation (splits = -1) needs the phased 256 x 256 form");
-        if (wg_phased && two_tiles)
-          hipLaunchKernelGGL(gemm_p256_grouped_kernel, dim3(b2), dim3(512), (size_t)2 * (256 + 256) * BK * 2, st, G, xcd_order);
-        else
-        hipLaunchKernelGGL((gemm_bf16_grouped_kernel<KS, KS, 2, 4, true, 4, 8>), dim3(b2), dim3(512),
-                           (size_t)2 * (256 + 256) * BK * 2, st, G, xcd_order);
-        FV_LAUNCH_CHECK();
-        continue;
-      }
-    }
-    FV_CHECK(!any_direct, "gemm_bf16_tn_grouped: in-place accumulation (splits = -1) is built for outputs that are multiples of 256 x 256 (>= 512 x 512) only");
-    // S-width outputs (d_model 384: in_proj 1536 x 384, out_proj 384 x 768 -- FastVim-S, FastChannelVim-S): 256 x 192 /
-    // 192 x 256 tiles on 8 waves, one workgroup per CU.  The launch is bound by the L2 -> LDS fill (see above): a 128 x 128
-    // tile moves 32 KB per 2.1 MFLOP of K step, these 56 KB per 6.3 -- 0.59 x the fill (gemm.py puts the two shapes in
-    // launches of their own)
-    {
-      // ONE rule decides (fv_gemm_bf16_tn_grouped_wide8: the host groups problems and picks split-K factors by it too --
-      // round 5 had the K threshold on the Python side only, so a launch Python had classed for 128 x 128 tiles could run
-      // on these with the wrong split factors)
-      bool c4 = dma && tile_env != 1, c5 = c4;
-      for (int i = 0; i < n; ++i) {
-        const int w8 = fv_gemm_bf16_tn_grouped_wide8(G.p[i].M, G.p[i].N, G.p[i].K);
-        c4 = c4 && w8 == 4;
-        c5 = c5 && w8 == 5;
-      }
-      if (c4 || c5) {
-        const int tm = c4 ? 256 : 192, tn = c4 ? 192 : 256;
-        int b2 = 0;
-        for (int i = 0; i < n; ++i) {
-          b2 += (G.p[i].M / tm) * (G.p[i].N / tn) * fv_cdiv(G.p[i].K, G.p[i].k_per_split);
-          G.blk_end[i] = b2;
-        }
-        const size_t sm8 = (size_t)2 * (256 + 192) * BK * 2;
-        static FvOncePerDevice attr8;
-        if (attr8.first()) {
-          (void)hipFuncSetAttribute((const void*)gemm_bf16_grouped_kernel<KS, KS, 4, 2, true, 6, 4>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm8);
-          (void)hipFuncSetAttribute((const void*)gemm_bf16_grouped_kernel<KS, KS, 2, 4, true, 4, 6>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm8);
-        }
-        if (c4) hipLaunchKernelGGL((gemm_bf16_grouped_kernel<KS, KS, 4, 2, true, 6, 4>), dim3(b2), dim3(512), sm8, st, G, xcd_order);
-        else hipLaunchKernelGGL((gemm_bf16_grouped_kernel<KS, KS, 2, 4, true, 4, 6>), dim3(b2), dim3(512), sm8, st, G, xcd_order);
-        FV_LAUNCH_CHECK();
-        continue;
-      }
-    }
     int blocks = 0;
     for (int i = 0; i < n; ++i) {
-      blocks += fv_cdiv(G.p[i].M, bm[cls]) * fv_cdiv(G.p[i].N, bn[cls]) * fv_cdiv(G.p[i].K, G.p[i].k_per_split);
+      blocks += fv_cdiv(G.p[i].M, kGroupedTileM[pl.cls]) * fv_cdiv(G.p[i].N, kGroupedTileN[pl.cls]) * fv_cdiv(G.p[i].K, G.p[i].k_per_split);
       G.blk_end[i] = blocks;
     }
-    const size_t smem = (size_t)2 * (bm[cls] + bn[cls]) * BK * 2;
-    // (256 x 192 tiles on 8 waves for the first class, half the L2 traffic again: 310 vs 316 us in the step in round 2 -- not
-    //  taken; again in round 3 with 6 / 8 / 12 / 14 K slices: step 5.73-5.84 against 5.68 ms, profiles/r03_ab_wgrad_t256_tiles.log)
-    if (cls == 1) {
-      static FvOncePerDevice attr;   
-      if (attr.first()) {
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_grouped_kernel<KS, KS, 2, 2, true, 6, 4>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)0;     
-      }
-      hipLaunchKernelGGL((gemm_bf16_grouped_kernel<KS, KS, 2, 2, true, 6, 4>), dim3(blocks), dim3(256), smem, st, G, xcd_order);
-    } else if (cls == 2) {
-      static FvOncePerDevice attr;   
-      if (attr.first()) {
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_grouped_kernel<KS, KS, 2, 2, true, 4, 6>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)0;     
-      }
-      hipLaunchKernelGGL((gemm_bf16_grouped_kernel<KS, KS, 2, 2, true, 4, 6>), dim3(blocks), dim3(256), smem, st, G, xcd_order);
-    } else if (dma) {
-      hipLaunchKernelGGL((gemm_bf16_grouped_kernel<KS, KS, 2, 2, true, 4, 4>), dim3(blocks), dim3(256), smem, st, G, xcd_order);
-    } else {
-      hipLaunchKernelGGL((gemm_bf16_grouped_kernel<KS, KS, 2, 2, false, 4, 4>), dim3(blocks), dim3(256), smem, st, G, xcd_order);
+    switch (pl.cls) {
+      case FV_GEMM_GROUPED_256x256:
+        if (pl.phased) {
+          static FvOncePerDevice attr;
+          if (attr.first())
+            (void)hipFuncSetAttribute((const void*)gemm_p256_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      2 * (256 + 256) * BK * 2);
+          hipLaunchKernelGGL(gemm_p256_grouped_kernel, dim3(blocks), dim3(512), (size_t)2 * (256 + 256) * BK * 2, st, G, xcd_order);
+        } else {
+          launch_grouped<2, 4, true, 4, 8>(G, blocks, xcd_order, st);
+        }
+        break;
+      case FV_GEMM_GROUPED_256x192: launch_grouped<4, 2, true, 6, 4>(G, blocks, xcd_order, st); break;
+      case FV_GEMM_GROUPED_192x256: launch_grouped<2, 4, true, 4, 6>(G, blocks, xcd_order, st); break;
+      case FV_GEMM_GROUPED_128x192: launch_grouped<2, 2, true, 6, 4>(G, blocks, xcd_order, st); break;
+      case FV_GEMM_GROUPED_192x128: launch_grouped<2, 2, true, 4, 6>(G, blocks, xcd_order, st); break;
+      default:
+        if (pl.dma) launch_grouped<2, 2, true, 4, 4>(G, blocks, xcd_order, st);
+        else launch_grouped<2, 2, false, 4, 4>(G, blocks, xcd_order, st);
     }
     FV_LAUNCH_CHECK();
   }
   return FV_OK;
 }
+
+// The plan of ONE launch of the grouped entry over these `count` problems (at most 40: the entry cuts longer lists into
+// balanced launches itself), from grouped_plan above -- the function the entry asks.  Returns the tile class
+// (FV_GEMM_GROUPED_*), or a negative value where the entry would refuse the problems on their shapes.
+extern "C" int fv_gemm_bf16_tn_grouped_plan(const int* Kd, const int* M, const int* N, const int* ldx, const int* ldy,
+                                            const int* splits, int count, int* lds_dma, int* phased) {
+  FV_CHECK(Kd && M && N && splits && count > 0 && count <= GROUP_MAX, "gemm_bf16_tn_grouped_plan: bad arguments (one launch: 1..%d problems)", GROUP_MAX);
+  GemmParams P[GROUP_MAX] = {};
+  for (int q = 0; q < count; ++q) {
+    const int rc = grouped_problem(P[q], q, Kd[q], M[q], N[q], ldx ? ldx[q] : M[q], ldy ? ldy[q] : N[q], splits[q]);
+    if (rc != FV_OK) return rc;
+  }
+  GroupedPlan pl{};
+  const int rc = grouped_plan(P, count, pl);
+  if (rc != FV_OK) return rc;
+  if (lds_dma) *lds_dma = pl.dma;
+  if (phased) *phased = pl.phased;
+  return pl.cls;
+}
+

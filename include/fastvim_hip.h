@@ -99,7 +99,10 @@ const char* fv_last_error(void);
  *      models' loader on planar uint8 planes: THE CELL RECORD below); no existing entry point changed.
  *      Later, still 3: fv_jpeg_sync_stage, fv_jpeg_sync_host, fv_jpeg_sync_table_ints and fv_jpeg_sync were ADDED (the
  *      entries fv_jpeg_huff starts from, found on the device without a sidecar index: ENTRIES MADE ON THE DEVICE below);
- *      no existing entry point, record layout or default changed. */
+ *      no existing entry point, record layout or default changed.
+ *      Later, still 3: fv_gemm_bf16_plan and fv_gemm_bf16_tn_grouped_plan were ADDED (the launch fv_gemm_bf16 and one launch
+ *      of fv_gemm_bf16_tn_grouped(_ld) make, answered by the deciders the launches themselves ask: FV_GEMM_KIND_*,
+ *      FV_GEMM_GROUPED_*); no existing entry point changed and every shape runs on the kernel it ran on. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -461,6 +464,26 @@ int fv_ln2d_bwd(const void* dy, const void* x, int dtype, const float* weight, c
 int fv_gemm_bf16(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda,
                  long ldb, long ldc, int a_k_slow, int b_k_slow, int c_fp32, int splits, fv_stream_t stream);
 
+/* The kernel fv_gemm_bf16 launches for these arguments, without launching it -- the answer of the ONE function the launch
+ * itself asks (a test names the kernel it means and asserts it before it runs).  Returns FV_GEMM_KIND_*, or the negative
+ * code with which fv_gemm_bf16 refuses the shape (pointers, their alignment and lda / ldb are not part of the question).
+ * has_bias: a bias pointer would be given; rb_period > 0: the call is fv_gemm_bf16_rowbias with that period.  cus: the CU
+ * count the rules that count workgroup rounds are asked for, 0 = the current device (256 where there is none).  tile_m /
+ * tile_n / lds_dma (nullable) receive the tile's extents and whether the operands are staged by LDS-DMA (1) or through
+ * registers (0).  A tuning build's extra tile shapes answer 100 + the value of their hook. */
+enum {
+  FV_GEMM_KIND_STREAM = 0,             /* persistent streaming kernel, 128 x 192 tiles of trimmed height */
+  FV_GEMM_KIND_PHASED_TILE = 1,        /* phased 256 x 256 kernel, one workgroup per tile */
+  FV_GEMM_KIND_PHASED_PERSISTENT = 2,  /* phased 256 x 256 kernel, one persistent workgroup per CU */
+  FV_GEMM_KIND_WAVE8_256 = 3,          /* 256 x 256 tiles on eight waves */
+  FV_GEMM_KIND_160x128 = 4,
+  FV_GEMM_KIND_128x96 = 5,
+  FV_GEMM_KIND_128x192 = 6,
+  FV_GEMM_KIND_128x128 = 7             /* the only kind with both staging forms */
+};
+int fv_gemm_bf16_plan(int M, int N, int K, int a_k_slow, int b_k_slow, int c_fp32, int has_bias, int rb_period, long ldc,
+                      int splits, int cus, int* tile_m, int* tile_n, int* lds_dma);
+
 /* fp32-MFMA GEMM (v_mfma_f32_16x16x4_f32), batched:  C_b[M][N] = sum_k A_b(m,k) B_b(k,n) (+ bias[n]),  b < batch.
  * The projections in the reference's DEFAULT precision (fp32, imagenet_classification/train.py:17) -- F.linear / matmul /
  * bmm behind in_proj, x_proj, out_proj, patch embed, head and their adjoints (mamba_simple_faster.py:189-193, 321-327,
@@ -643,6 +666,22 @@ int fv_gemm_bf16_tn_grouped_ld(const void* const* x, const void* const* y, float
  * 4 = 256 x 192 tiles, 5 = 192 x 256 tiles (eight waves; the d_model-384 outputs from 50 000 tokens on), 0 = not taken.  The
  * host groups problems per launch and picks their split-K factors by the same answer. */
 int fv_gemm_bf16_tn_grouped_wide8(int M, int N, int Kd);
+
+/* The plan of ONE launch of fv_gemm_bf16_tn_grouped_ld over these problems (1 .. 40 of them; the entry cuts a longer list
+ * into balanced launches of at most 40), from the function the entry itself asks.  Arrays as the entry takes them (ldx /
+ * ldy nullable).  Returns the tile class FV_GEMM_GROUPED_*, or the negative code with which the entry refuses the problems
+ * on their shapes (splits = -1 off the phased form, a K that does not cut into whole tiles, ...).  lds_dma (nullable): 1 =
+ * operands staged by LDS-DMA, 0 = through registers (128 x 128 only); phased (nullable): 1 = the phased 256 x 256 form. */
+enum {
+  FV_GEMM_GROUPED_128x128 = 0,
+  FV_GEMM_GROUPED_128x192 = 1,
+  FV_GEMM_GROUPED_192x128 = 2,
+  FV_GEMM_GROUPED_256x256 = 3,         /* eight waves; phased when every slice has two K tiles or more */
+  FV_GEMM_GROUPED_256x192 = 4,         /* eight waves: fv_gemm_bf16_tn_grouped_wide8 */
+  FV_GEMM_GROUPED_192x256 = 5
+};
+int fv_gemm_bf16_tn_grouped_plan(const int* Kd, const int* M, const int* N, const int* ldx, const int* ldy,
+                                 const int* splits, int count, int* lds_dma, int* phased);
 
 /* x_proj of both directions, bf16: x_dbl (2, M, width) = xc (2, M, d_inner) @ x_proj_w2 (2, width, d_inner)^T, fp32
  * accumulate (mamba_simple_faster.py:321-327; the F.linear behind `self.x_proj` / `self.x_proj_b`).  M = batch*Lc,
