@@ -51,6 +51,7 @@ C_ABI_SYMBOLS = (
     "fv_cellaug_geom", "fv_cellaug_filter",
     "fv_jpeg_sync_stage", "fv_jpeg_sync_host", "fv_jpeg_sync_table_ints", "fv_jpeg_sync",
     "fv_gemm_bf16_plan", "fv_gemm_bf16_tn_grouped_plan",
+    "fv_mae_encoder_tokens_cls_fwd", "fv_mae_encoder_tokens_cls_bwd", "fv_mae_decoder_tokens_cls_fwd", "fv_mae_decoder_tokens_cls_bwd",
 )
 
 

@@ -19,6 +19,7 @@
 //                              one -- rounded to x's type first, as autograd rounds it -- is added to the workgroup's fp64
 //                              partial in row order; mae_decoder_tokens_final sums the partials in fp64 in a fixed order
 //                              (sixteen strided walks, then a fixed tree).  No atomics: the same inputs give the same bits.
+//                              Both kernels live in mae_tokens_common.h: mae_tokens_cls.hip launches them too.
 // Floating-point reassociation and contraction are switched off for the whole file: every sum has ONE order, the one written.
 #include "common.h"
 #include "mask_noise.h"
@@ -26,11 +27,11 @@
 
 #pragma clang fp reassociate(off) contract(off)
 
+#include "mae_tokens_common.h"      // (behind the pragma: the fixed-order sum mae_tokens_cls.hip shares)
+
 namespace {
 
 constexpr int MP_MAX_L = FV_MAE_PLAN_MAX_TOKENS;
-constexpr int DT_ROWS = FV_MAE_DECODER_ROWS_PER_BLOCK;
-constexpr int DT_FINAL_WAVES = 16;
 
 struct PlanOut {
   long long* ids_keep;      // (B, K)
@@ -221,69 +222,6 @@ __global__ __launch_bounds__(256) void mae_decoder_tokens_fwd_kernel(const TX* _
   VecIO<float, 4>::store(out + (size_t)row * D + c, v);
 }
 
-// A workgroup owns rows [blockIdx.x DT_ROWS, + DT_ROWS) of the (B L) rows of dout; a thread owns 4 channels of them.
-template <typename TX>
-__global__ __launch_bounds__(256) void mae_decoder_tokens_bwd_kernel(const float* __restrict__ dout, const int* __restrict__ restore,
-                                                                     TX* __restrict__ dx, double* __restrict__ partials, long rows,
-                                                                     int L, int K, int D) {
-  const long r0 = (long)blockIdx.x * DT_ROWS;
-  const long r1 = r0 + DT_ROWS < rows ? r0 + DT_ROWS : rows;
-  for (int c = threadIdx.x * 4; c < D; c += blockDim.x * 4) {
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (long row = r0; row < r1; ++row) {
-      const int r = restore[row];         // wave-uniform
-      float v[4];
-      VecIO<float, 4>::load(dout + (size_t)row * D + c, v);
-      if (r >= 0 && r < K) {
-        const long b = row / L;
-        VecIO<TX, 4>::store(dx + ((size_t)b * K + r) * D + c, v);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float t = v[e];
-          if constexpr (sizeof(TX) == 2) t = bf16_bits_to_f32(f32_to_bf16_bits(t));
-          acc[e] += (double)t;
-        }
-      }
-    }
-    double* dst = partials + (size_t)blockIdx.x * D + c;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) dst[e] = acc[e];
-  }
-}
-
-// A workgroup of 16 waves owns 64 channels: wave w adds partial rows w, w + 16, ... in that order, then the sixteen sums
-// are added as a fixed tree.  All in fp64; one rounding, to fp32, at the end.
-__global__ __launch_bounds__(64 * DT_FINAL_WAVES) void mae_decoder_tokens_final_kernel(const double* __restrict__ partials,
-                                                                                       float* __restrict__ dmask_token, int nblocks,
-                                                                                       int D) {
-  __shared__ double s[DT_FINAL_WAVES][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;
-  double acc = 0.0;
-  if (c < D) {
-#pragma unroll 4
-    for (int k = wave; k < nblocks; k += DT_FINAL_WAVES) acc += partials[(size_t)k * D + c];
-  }
-  s[wave][lane] = acc;
-  __syncthreads();
-  if (wave == 0 && c < D) {
-    double t[DT_FINAL_WAVES];
-#pragma unroll
-    for (int k = 0; k < DT_FINAL_WAVES; ++k) t[k] = s[k][lane];
-#pragma unroll
-    for (int w = DT_FINAL_WAVES / 2; w > 0; w >>= 1) {
-#pragma unroll
-      for (int k = 0; k < w; ++k) t[k] = t[2 * k] + t[2 * k + 1];
-    }
-    dmask_token[c] = (float)t[0];
-  }
-}
-
-bool f32_or_bf16(int dt) { return dt == FV_F32 || dt == FV_BF16; }
-size_t esize(int dt) { return dt == FV_F32 ? 4 : 2; }
-bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
-
 }  // namespace
 
 namespace {
@@ -413,13 +351,13 @@ extern "C" int fv_mae_decoder_tokens_bwd(const float* dout, const int* restore_i
   const int nblocks = fv_cdiv(rows, DT_ROWS);
   FV_CHECK(n_partials == nblocks, "mae_decoder_tokens_bwd: partials must hold ceil(batch len / %d) = %d rows of dim doubles, got %d",
            DT_ROWS, nblocks, n_partials);
-  const int threads = dim / 4 >= 256 ? 256 : (dim / 4 > 64 ? ((dim / 4 + 63) / 64) * 64 : 64);
+  const int threads = row_walk_threads(dim);
   hipStream_t st = (hipStream_t)stream;
   if (x_dtype == FV_BF16)
-    hipLaunchKernelGGL(mae_decoder_tokens_bwd_kernel<bf16_t>, dim3(nblocks), dim3(threads), 0, st, dout, restore_index, (bf16_t*)dx,
+    hipLaunchKernelGGL((mae_decoder_tokens_bwd_kernel<bf16_t, false>), dim3(nblocks), dim3(threads), 0, st, dout, restore_index, (bf16_t*)dx,
                        partials, rows, len, len_keep, dim);
   else
-    hipLaunchKernelGGL(mae_decoder_tokens_bwd_kernel<float>, dim3(nblocks), dim3(threads), 0, st, dout, restore_index, (float*)dx,
+    hipLaunchKernelGGL((mae_decoder_tokens_bwd_kernel<float, false>), dim3(nblocks), dim3(threads), 0, st, dout, restore_index, (float*)dx,
                        partials, rows, len, len_keep, dim);
   hipLaunchKernelGGL(mae_decoder_tokens_final_kernel, dim3(fv_cdiv(dim, 64)), dim3(64 * DT_FINAL_WAVES), 0, st,
                      (const double*)partials, dmask_token, nblocks, dim);

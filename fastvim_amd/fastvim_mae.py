@@ -7,6 +7,11 @@ Encoder and decoder are plain Vim blocks on the un-pooled Vim mixer (fastvim_amd
 the encoder over the kept tokens with the class token in their middle, the decoder over the full grid with the class
 token appended -- on the same fused HIP kernels as the FastVim MAE (fastvim_amd/models_mae.py), whose host-side helpers
 (patchify, masking with a ``noise`` hook, loss, final norm) it inherits.
+
+``fused_tokens`` (or a ``sampler``, the opt-in of the graph-replayed ``fastvim_amd.mae_step.VimMAEPretrainStep``): the token
+bookkeeping around the class token -- encoder input and decoder input -- is one launch each way on the step's ``TokenPlan``
+(fastvim_amd/mae_tokens.py: ``encoder_tokens_cls``, ``decoder_tokens_cls``) instead of the torch chain; same values, with
+``cls_token.grad`` and ``mask_token.grad`` up to their summation order.
 """
 from functools import partial
 
@@ -14,6 +19,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import mae_tokens
 from .fastvim import _init_weights, trunc_normal_
 from .layernorm import RMSNorm
 from .mamba_simple_faster import linear_module
@@ -88,41 +94,90 @@ class MaskedAutoencoderViM(_FastVimMAE):
 
     # The class token sits in the middle of the kept tokens and the blocks take no plan: this model does not share the FastVim
     # MAE's loops, so it does not offer the segment protocol of fastvim_amd.mae_step.MAEPretrainStep (which names the
-    # missing method in its TypeError).
+    # missing method in its TypeError).  Its own protocol, for fastvim_amd.mae_step.VimMAEPretrainStep, is the ``_cls`` trio
+    # below.
     _embed_masked = _run_layers = _tail = None
 
-    def forward_encoder(self, x, mask_ratio, inference_params=None, noise=None, sampler=None):
-        """:583-631: patch embedding + position (the class slot of ``pos_embed`` goes to the class token), masking, the
-        class token in the MIDDLE of the kept tokens, Vim blocks, final norm."""
-        x = self.patch_embed(x, self.pos_embed[:, 1:, :])
-        x, mask, ids_restore, _ = self.random_masking(x, mask_ratio, noise, sampler)
+    def _mask_with_cls(self, x, mask_ratio, noise=None, sampler=None):
+        """Masking and the class token in the MIDDLE of the kept tokens (:590-607) -> (tokens (N, K + 1, D), mask,
+        ids_restore, plan).  ``x``: the patch embedding with its position rows added.
+
+        ``fused_tokens`` or a ``sampler``: the inherited ``_masking`` makes the step's ``TokenPlan`` (where its predicate
+        holds) and ``mae_tokens.encoder_tokens_cls`` assembles the tokens from the un-gathered ``x`` in one launch; where
+        that says no, the torch chain runs on the gathered tokens.  Neither: ``plan`` is None and the code is the
+        reference's, line for line."""
+        plan = None
+        if self.fused_tokens or sampler is not None:
+            kept, mask, ids_restore, _, plan = self._masking(x, mask_ratio, noise, sampler, gather=False)
+            if plan is not None:
+                if mae_tokens.encoder_tokens_cls_ok(x, self.cls_token, self.pos_embed, plan):
+                    return mae_tokens.encoder_tokens_cls(x, self.cls_token, self.pos_embed, plan), mask, ids_restore, plan
+                kept = mae_tokens.gather_tokens(x, plan.keep_index, plan.restore_index)
+            x = kept
+        else:
+            x, mask, ids_restore, _ = self.random_masking(x, mask_ratio, noise, sampler)
         M = x.shape[1]
         cls_tokens = (self.cls_token + self.pos_embed[:, :1, :]).expand(x.shape[0], -1, -1).to(x.dtype)
         token_position = M // 2
         x = torch.cat((x[:, :token_position, :], cls_tokens, x[:, token_position:, :]), dim=1)
+        return x, mask, ids_restore, plan
+
+    def forward_encoder(self, x, mask_ratio, inference_params=None, noise=None, sampler=None):
+        """:583-631: patch embedding + position (the class slot of ``pos_embed`` goes to the class token), masking, the
+        class token in the MIDDLE of the kept tokens, Vim blocks, final norm."""
+        return self._encode(x, mask_ratio, inference_params, noise=noise, sampler=sampler)[:3]
+
+    def _encode(self, x, mask_ratio, inference_params=None, noise=None, sampler=None):
+        """``forward_encoder`` plus the step's ``TokenPlan`` (or None) as a fourth value, for ``forward_decoder``."""
+        x = self.patch_embed(x, self.pos_embed[:, 1:, :])
+        x, mask, ids_restore, plan = self._mask_with_cls(x, mask_ratio, noise, sampler)
         residual = None
         hidden_states = x
         for layer in self.layers:
             hidden_states, residual = layer(hidden_states, residual, inference_params=inference_params)
-        return self._final_norm(self.norm_f, hidden_states, residual), mask, ids_restore
+        return self._final_norm(self.norm_f, hidden_states, residual), mask, ids_restore, plan
 
-    def _encode(self, x, mask_ratio, inference_params=None, noise=None, sampler=None):
-        # ``fused_tokens`` (and a ``sampler``'s keyed plan) reach the inherited ``random_masking`` only: the decoder assembly
-        # below, with its class token, keeps the torch chain, so no plan is handed on
-        return (*self.forward_encoder(x, mask_ratio, inference_params, noise=noise, sampler=sampler), None)
+    # ---- the segment protocol of fastvim_amd.mae_step.VimMAEPretrainStep: the FastVim MAE's (_embed_masked / _run_layers /
+    # _tail) under names of its own -- the blocks take no plan, the tokens carry the class token.
+    def _embed_masked_cls(self, imgs, mask_ratio, sampler):
+        """Patch embedding + masking + the class token -> (tokens (N, K + 1, D), plan).  The keyed plan must apply."""
+        x = self.patch_embed(imgs, self.pos_embed[:, 1:, :])
+        tokens, _, _, plan = self._mask_with_cls(x, mask_ratio, None, sampler)
+        if plan is None:
+            raise RuntimeError("MaskedAutoencoderViM._embed_masked_cls: the keyed masking plan does not take these tokens "
+                               f"({tuple(x.shape)} {x.dtype}, grid {tuple(self.token_size)}); see mae_tokens.plan_shape_ok")
+        return tokens, plan
 
-    def forward_decoder(self, x, ids_restore, inference_params=None):
+    def _run_layers_cls(self, hidden_states, residual, lo, hi, plan):
+        """Encoder blocks ``lo .. hi - 1``; plain Vim blocks, which do not read the plan."""
+        for layer in self.layers[lo:hi]:
+            hidden_states, residual = layer(hidden_states, residual, inference_params=None)
+        return hidden_states, residual
+
+    def _tail_cls(self, hidden_states, residual, imgs, plan):
+        """``norm_f``, the decoder and the reconstruction loss -> (loss, pred)."""
+        latent = self._final_norm(self.norm_f, hidden_states, residual)
+        pred = self.forward_decoder(latent, plan.ids_restore, plan=plan)
+        return self._loss(imgs, pred, plan.mask), pred
+
+    def forward_decoder(self, x, ids_restore, inference_params=None, plan=None):
         """:633-691: mask tokens appended and unshuffled WITHOUT the class token, which is re-attached at the END of the
-        sequence, carried through the decoder blocks and dropped from the prediction."""
+        sequence, carried through the decoder blocks and dropped from the prediction.  ``plan``: the ``TokenPlan`` that
+        ``ids_restore`` came from -- the decoder's input is then assembled by ``mae_tokens.decoder_tokens_cls`` where it takes
+        the tensors; None: the torch chain."""
         token_position = (x.shape[1] - 1) // 2
         x = linear_module(self.decoder_embed, x)
-        mask_tokens = self.mask_token.repeat(x.shape[0], ids_restore.shape[1] + 1 - x.shape[1], 1).to(x.dtype)
-        x_ = torch.cat([x[:, :token_position, :], x[:, token_position + 1:, :], mask_tokens], dim=1)      # no cls token
-        x_ = torch.gather(x_, dim=1, index=ids_restore.unsqueeze(-1).repeat(1, 1, x.shape[2]))            # unshuffle
-        x_ = x_ + self.decoder_pos_embed[:, 1:]
-        cls_tokens = x[:, token_position:token_position + 1, :] + self.decoder_pos_embed[:, :1, :]
-        n = x_.shape[1]
-        x = torch.cat([x_, cls_tokens.to(x_.dtype)], dim=1)
+        if plan is not None and mae_tokens.decoder_tokens_cls_ok(x, self.mask_token, self.decoder_pos_embed, plan):
+            x = mae_tokens.decoder_tokens_cls(x, self.mask_token, self.decoder_pos_embed, plan)
+            n = x.shape[1] - 1
+        else:
+            mask_tokens = self.mask_token.repeat(x.shape[0], ids_restore.shape[1] + 1 - x.shape[1], 1).to(x.dtype)
+            x_ = torch.cat([x[:, :token_position, :], x[:, token_position + 1:, :], mask_tokens], dim=1)      # no cls token
+            x_ = torch.gather(x_, dim=1, index=ids_restore.unsqueeze(-1).repeat(1, 1, x.shape[2]))            # unshuffle
+            x_ = x_ + self.decoder_pos_embed[:, 1:]
+            cls_tokens = x[:, token_position:token_position + 1, :] + self.decoder_pos_embed[:, :1, :]
+            n = x_.shape[1]
+            x = torch.cat([x_, cls_tokens.to(x_.dtype)], dim=1)
         residual = None
         for layer in self.decoder_blocks:
             x, residual = layer(x, residual, inference_params=inference_params)

@@ -44,13 +44,16 @@ class MAEPretrainStep:
     snapshotted before and put back after them, so constructing the step leaves everything as it found it and the first
     ``micro_step()`` is step 0 of the trajectory.  ``use_graph=False`` runs the same sequence eagerly."""
 
+    # the model's three segment methods -- embed + mask, a run of encoder blocks, the tail -- and the class that has them
+    _protocol = _PROTOCOL
+    _model_class = "fastvim_amd.models_mae.MaskedAutoencoderViM"
+
     def __init__(self, model, flat, opt, x, sampler, mask_ratio=0.75, accum_iter=1, n_segments=3, amp_dtype=torch.bfloat16,
                  use_graph=True, warmup=2):
-        for name in _PROTOCOL:
+        for name in self._protocol:
             if not callable(getattr(model, name, None)):
-                raise TypeError(f"MAEPretrainStep: {type(model).__module__}.{type(model).__name__} has no {name}() -- the step "
-                                "cuts the encoder of fastvim_amd.models_mae.MaskedAutoencoderViM into runs of blocks that "
-                                "share one masking plan")
+                raise TypeError(f"{type(self).__name__}: {type(model).__module__}.{type(model).__name__} has no {name}() -- the "
+                                f"step cuts the encoder of {self._model_class} into runs of blocks that share one masking plan")
         if int(accum_iter) < 1:
             raise ValueError(f"MAEPretrainStep: accum_iter must be at least 1, got {accum_iter}")
         if not model.training:
@@ -81,9 +84,10 @@ class MAEPretrainStep:
     # ------------------------------------------------------------------ the pieces
     def _forward(self):
         m = self.model
+        embed_masked, run_layers, tail = (getattr(m, name) for name in self._protocol)
         cuts = []              # per run in FORWARD order: (inputs (leaves) or None, outputs)
         with torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.amp_dtype != torch.float32):
-            h, plan = m._embed_masked(self.x, self.mask_ratio, self.sampler)
+            h, plan = embed_masked(self.x, self.mask_ratio, self.sampler)
             res = None
             for i, (lo, hi) in enumerate(self.runs[::-1]):
                 if i > 0:          # cut: this run's inputs are leaves that alias the previous run's outputs
@@ -91,9 +95,9 @@ class MAEPretrainStep:
                     ins = (h, res)
                 else:
                     ins = None
-                h, res = m._run_layers(h, res, lo, hi, plan)
+                h, res = run_layers(h, res, lo, hi, plan)
                 cuts.append([ins, (h, res)])
-            loss, _ = m._tail(h, res, self.x, plan)
+            loss, _ = tail(h, res, self.x, plan)
         cuts[-1][1] = (loss,)
         self._cuts = cuts
         self.mask = plan.mask
@@ -203,3 +207,26 @@ class MAEPretrainStep:
             with torch.no_grad():
                 self.flat.grad_flat.copy_(state["grad_flat"])
         self._micro = micro
+
+
+class VimMAEPretrainStep(MAEPretrainStep):
+    """The same step for the Vim MAE baseline, ``fastvim_amd.fastvim_mae.MaskedAutoencoderViM`` (the reference's
+    mae/config/pretrain_Vim{B,L}.yaml): the un-pooled encoder with a class token in the middle of the kept tokens.  The model
+    offers the segment methods under names of its own (``_embed_masked_cls / _run_layers_cls / _tail_cls``; a model without
+    them -- the FastVim MAE -- raises ``TypeError``); everything else is ``MAEPretrainStep``: ``micro_step()``,
+    ``optimizer_ran``, ``mask``, ``accum_iter``, ``n_segments``, ``use_graph``, ``state_dict`` / ``load_state_dict``, and a
+    construction that leaves the training state, both RNG streams and the sampler's counter as it found them.
+
+    The forward graph holds the patch embedding, the keyed plan, ``mae_tokens.encoder_tokens_cls`` (the tokens of width
+    K + 1 every run of blocks then carries), the blocks, ``norm_f``, the decoder behind ``mae_tokens.decoder_tokens_cls`` and
+    the loss.  ``x`` may be the uint8 batch after ``fastvim_amd.pixels.attach_pixel_norm``: the model's patch embedding is the
+    FastVim one in row-major order (fastvim_amd/vim.py: ``PatchEmbed``), which the pixel table serves.
+
+    Flat layout (fastvim_amd/flat.py): ``cls_token`` and ``mask_token`` are parameters of the model itself, so both lie in
+    the unit IN FRONT of the block stack, with the patch embedding -- ``[cls_token, mask_token, patch_embed | layers.0 ..
+    layers.n | norm_f, decoder_*]``.  ``mask_token.grad`` is complete after backward graph 0 (the decoder), ``cls_token.grad``
+    only after the last one (the run that holds the embedding); the front unit belongs to the bucket ``make_exchange``
+    launches last, behind that graph, so both are exchanged complete."""
+
+    _protocol = tuple(name + "_cls" for name in _PROTOCOL)
+    _model_class = "fastvim_amd.fastvim_mae.MaskedAutoencoderViM"

@@ -9,6 +9,10 @@ a gather is the gather by the inverse index -- one pass, no zero fill, no atomic
 ``torch.gather`` composition and its autograd.  The one value that is not bit-identical is the gradient of ``mask_token``: a
 sum over the removed rows, here in fp64 in a fixed order (deterministic), in eager in whatever order the reduction takes.
 
+The Vim MAE baseline (fastvim_amd/fastvim_mae.py) carries a class token -- in the middle of the kept tokens in the encoder,
+behind the grid in the decoder: ``encoder_tokens_cls`` and ``decoder_tokens_cls`` (csrc/mae_tokens_cls.hip) are its two
+assemblies, one launch each way, on the same plan.
+
 Nothing here synchronises with the host; outputs are allocated by torch on the current stream: safe under graph capture.
 """
 import struct
@@ -289,3 +293,123 @@ def decoder_tokens(x, mask_token, pos_embed, plan):
                            f"{tuple(mask_token.shape)} {mask_token.dtype}, pos_embed {tuple(pos_embed.shape)} {pos_embed.dtype}); "
                            "see decoder_tokens_ok")
     return _DecoderTokensFn.apply(x, mask_token, pos_embed, plan.restore_index)
+
+
+# ---------------------------------------------------------------------------------------------- with a class token
+def _cls_common_ok(x, vec, pos_embed, plan, Ln, K, D):
+    """The part both class-token predicates share: ``vec`` (``cls_token`` / ``mask_token``) D fp32 values, ``pos_embed`` the
+    whole (1, L + 1, D) fp32 table without a gradient, the plan that of x's batch, everything on x's device."""
+    B = x.shape[0]
+    if tuple(plan.restore_index.shape) != (B, Ln) or tuple(plan.keep_index.shape) != (B, K):
+        return False
+    if plan.restore_index.device != x.device or plan.keep_index.device != x.device:
+        return False
+    return (vec.dtype == torch.float32 and vec.numel() == D and vec.is_contiguous() and vec.device == x.device
+            and pos_embed.dtype == torch.float32 and pos_embed.numel() == (Ln + 1) * D and pos_embed.is_contiguous()
+            and pos_embed.device == x.device and not pos_embed.requires_grad)
+
+
+def encoder_tokens_cls_ok(x, cls_token, pos_embed, plan):
+    """Whether ``encoder_tokens_cls`` takes these tensors (the model's fallback is the eager chain): ``x`` (B, L, D) fp32 or
+    bf16 on the GPU with D % 4 == 0, ``cls_token`` D fp32 values, ``pos_embed`` (1, L + 1, D) fp32 that does not require grad,
+    ``plan`` a ``TokenPlan`` of B samples and L tokens.  Pure Python: no GPU and no library needed to ask."""
+    if x.dim() != 3 or not x.is_cuda or x.dtype not in _DTYPES or x.shape[-1] % 4 != 0:
+        return False
+    B, Ln, D = x.shape
+    return _cls_common_ok(x, cls_token, pos_embed, plan, Ln, plan.keep_index.shape[1], D)
+
+
+def decoder_tokens_cls_ok(x, mask_token, pos_embed, plan):
+    """Whether ``decoder_tokens_cls`` takes these tensors: ``x`` (B, K + 1, D) -- the plan's K kept tokens and the class
+    token -- otherwise as ``encoder_tokens_cls_ok``, with ``mask_token`` in the place of ``cls_token``."""
+    if x.dim() != 3 or not x.is_cuda or x.dtype not in _DTYPES or x.shape[-1] % 4 != 0:
+        return False
+    B, K1, D = x.shape
+    return _cls_common_ok(x, mask_token, pos_embed, plan, plan.restore_index.shape[1], K1 - 1, D)
+
+
+class _EncoderTokensClsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, cls_token, pos_embed, keep_index, restore_index):
+        B, Ln, D = x.shape
+        K = keep_index.shape[1]
+        xc = x.contiguous()
+        out = torch.empty(B, K + 1, D, device=x.device, dtype=x.dtype)
+        rc = L.lib().fv_mae_encoder_tokens_cls_fwd(L.ptr(xc), L.i32(L.dtype_code(xc.dtype)), L.ptr(cls_token), L.ptr(pos_embed),
+                                                   L.ptr(keep_index), L.ptr(out), L.i32(B), L.i32(Ln), L.i32(K), L.i32(D),
+                                                   L.stream_of(xc))
+        L.check(rc, "mae_encoder_tokens_cls_fwd")
+        ctx.save_for_backward(restore_index)
+        ctx.geo = (B, Ln, K, D, x.dtype, tuple(cls_token.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (restore_index,) = ctx.saved_tensors
+        B, Ln, K, D, x_dtype, ct_shape = ctx.geo
+        dout = dout.to(x_dtype).contiguous()
+        dx = torch.empty(B, Ln, D, device=dout.device, dtype=x_dtype)
+        dct = torch.empty(D, device=dout.device, dtype=torch.float32)
+        rc = L.lib().fv_mae_encoder_tokens_cls_bwd(L.ptr(dout), L.ptr(restore_index), L.ptr(dx), L.i32(L.dtype_code(x_dtype)),
+                                                   L.ptr(dct), L.i32(B), L.i32(Ln), L.i32(K), L.i32(D), L.stream_of(dout))
+        L.check(rc, "mae_encoder_tokens_cls_bwd")
+        return dx, dct.view(ct_shape), None, None, None
+
+
+def encoder_tokens_cls(x, cls_token, pos_embed, plan):
+    """The Vim MAE encoder's input from one launch: ``x`` (B, L, D) fp32 or bf16, the patch embedding with its position rows
+    added, NOT yet gathered; ``cls_token`` (1, 1, D) fp32; ``pos_embed`` (1, L + 1, D) fp32, no gradient (its class slot, row
+    0, is what is read); ``plan`` the step's ``TokenPlan`` -> (B, K + 1, D) in ``x``'s dtype: the K kept tokens with
+    ``cls_token + pos_embed[:, :1]`` (added in fp32, rounded once) at place K // 2 -- the values of the eager ``gather /
+    add / expand / cast / cat`` chain.  Backward: ``dx`` (every row written, zero for the removed tokens) bit-identical to
+    autograd's; ``d cls_token`` the sum of the class rows over the batch, in fp64 in the order of the samples."""
+    if not encoder_tokens_cls_ok(x, cls_token, pos_embed, plan):
+        raise RuntimeError(f"encoder_tokens_cls: unsupported arguments (x {tuple(x.shape)} {x.dtype}, cls_token "
+                           f"{tuple(cls_token.shape)} {cls_token.dtype}, pos_embed {tuple(pos_embed.shape)} {pos_embed.dtype}); "
+                           "see encoder_tokens_cls_ok")
+    return _EncoderTokensClsFn.apply(x, cls_token, pos_embed, plan.keep_index, plan.restore_index)
+
+
+class _DecoderTokensClsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mask_token, pos_embed, restore_index):
+        B, K1, D = x.shape
+        Ln = restore_index.shape[1]
+        xc = x.contiguous()
+        out = torch.empty(B, Ln + 1, D, device=x.device, dtype=torch.float32)
+        rc = L.lib().fv_mae_decoder_tokens_cls_fwd(L.ptr(xc), L.i32(L.dtype_code(xc.dtype)), L.ptr(mask_token), L.ptr(pos_embed),
+                                                   L.ptr(restore_index), L.ptr(out), L.i32(B), L.i32(Ln), L.i32(K1 - 1), L.i32(D),
+                                                   L.stream_of(xc))
+        L.check(rc, "mae_decoder_tokens_cls_fwd")
+        ctx.save_for_backward(restore_index)
+        ctx.geo = (B, Ln, K1 - 1, D, x.dtype, tuple(mask_token.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (restore_index,) = ctx.saved_tensors
+        B, Ln, K, D, x_dtype, mt_shape = ctx.geo
+        dout = dout.float().contiguous()
+        dx = torch.empty(B, K + 1, D, device=dout.device, dtype=x_dtype)
+        nblocks = -(-(B * (Ln + 1)) // DECODER_ROWS_PER_BLOCK)
+        partials = torch.empty(nblocks, D, device=dout.device, dtype=torch.float64)
+        dmt = torch.empty(D, device=dout.device, dtype=torch.float32)
+        rc = L.lib().fv_mae_decoder_tokens_cls_bwd(L.ptr(dout), L.ptr(restore_index), L.ptr(dx), L.i32(L.dtype_code(x_dtype)),
+                                                   L.ptr(partials), L.i32(nblocks), L.ptr(dmt), L.i32(B), L.i32(Ln), L.i32(K),
+                                                   L.i32(D), L.stream_of(dout))
+        L.check(rc, "mae_decoder_tokens_cls_bwd")
+        return dx, dmt.view(mt_shape), None, None
+
+
+def decoder_tokens_cls(x, mask_token, pos_embed, plan):
+    """The Vim MAE decoder's input from one launch: ``x`` (B, K + 1, D) fp32 or bf16, ``decoder_embed`` of the encoder's
+    output (class token at place K // 2); ``mask_token`` (1, 1, D) fp32; ``pos_embed`` (1, L + 1, D) fp32, no gradient;
+    ``plan`` the step's ``TokenPlan`` -> (B, L + 1, D) fp32: rows 0 .. L-1 as ``decoder_tokens`` makes them from the tokens
+    without the class token and ``pos_embed[:, 1:]``, row L the class token + ``pos_embed[:, :1]`` -- the values, dtype and
+    single rounding of the eager ``cat / repeat / cat / gather / add / add / cat`` chain.  Backward as ``decoder_tokens``;
+    the class row is no mask row."""
+    if not decoder_tokens_cls_ok(x, mask_token, pos_embed, plan):
+        raise RuntimeError(f"decoder_tokens_cls: unsupported arguments (x {tuple(x.shape)} {x.dtype}, mask_token "
+                           f"{tuple(mask_token.shape)} {mask_token.dtype}, pos_embed {tuple(pos_embed.shape)} {pos_embed.dtype}); "
+                           "see decoder_tokens_cls_ok")
+    return _DecoderTokensClsFn.apply(x, mask_token, pos_embed, plan.restore_index)

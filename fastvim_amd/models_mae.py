@@ -250,10 +250,11 @@ class MaskedAutoencoderViM(nn.Module):
         mixers are sequential (models_mamba_faster_mae_vimdecoder.py:738-772)."""
         return self._masking(x, mask_ratio, noise, sampler)[:4]
 
-    def _masking(self, x, mask_ratio, noise=None, sampler=None):
+    def _masking(self, x, mask_ratio, noise=None, sampler=None, gather=True):
         """``random_masking`` plus the step's ``TokenPlan`` as a fifth value: None unless ``fused_tokens`` is set and
         ``mae_tokens.mask_plan_ok`` holds (then the plan's launch replaces the index code and the gather is
-        ``gather_tokens``; same four values).
+        ``gather_tokens``; same four values).  ``gather=False``: where a plan is made the kept tokens are NOT gathered and
+        the first value is None -- the caller's own launch reads ``x`` through the plan (fastvim_amd/fastvim_mae.py).
 
         ``sampler`` (a ``mae_tokens.MaskSampler``): the noise is the sampler's, a function of its (seed, counter).  Where
         the plan's predicate holds the keyed plan launch makes it in registers -- the sampler is the opt-in, whatever
@@ -267,7 +268,7 @@ class MaskedAutoencoderViM(nn.Module):
                     and L == int(self.token_size[0]) * int(self.token_size[1])
                     and mae_tokens.plan_shape_ok(N, self.token_size, len_keep)):
                 plan = mae_tokens.mask_plan_keyed(sampler, N, self.token_size, len_keep, device=x.device)
-                x_masked = mae_tokens.gather_tokens(x, plan.keep_index, plan.restore_index)
+                x_masked = mae_tokens.gather_tokens(x, plan.keep_index, plan.restore_index) if gather else None
                 return x_masked, plan.mask, plan.ids_restore, plan.ids_keep, plan
             noise = sampler.noise(N, L, device=x.device)
         if noise is None:
@@ -276,7 +277,7 @@ class MaskedAutoencoderViM(nn.Module):
                 and noise.device == x.device and tuple(noise.shape) == (N, L)
                 and mae_tokens.mask_plan_ok(noise, self.token_size, len_keep)):
             plan = mae_tokens.mask_plan(noise, self.token_size, len_keep)
-            x_masked = mae_tokens.gather_tokens(x, plan.keep_index, plan.restore_index)
+            x_masked = mae_tokens.gather_tokens(x, plan.keep_index, plan.restore_index) if gather else None
             return x_masked, plan.mask, plan.ids_restore, plan.ids_keep, plan
         ids_shuffle = torch.argsort(noise, dim=1)          # ascend: small is keep, large is remove
         ids_shuffle[:, :len_keep] = ids_shuffle[:, :len_keep].sort().values

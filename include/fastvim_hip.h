@@ -102,7 +102,10 @@ const char* fv_last_error(void);
  *      no existing entry point, record layout or default changed.
  *      Later, still 3: fv_gemm_bf16_plan and fv_gemm_bf16_tn_grouped_plan were ADDED (the launch fv_gemm_bf16 and one launch
  *      of fv_gemm_bf16_tn_grouped(_ld) make, answered by the deciders the launches themselves ask: FV_GEMM_KIND_*,
- *      FV_GEMM_GROUPED_*); no existing entry point changed and every shape runs on the kernel it ran on. */
+ *      FV_GEMM_GROUPED_*); no existing entry point changed and every shape runs on the kernel it ran on.
+ *      Later, still 3: fv_mae_encoder_tokens_cls_fwd, fv_mae_encoder_tokens_cls_bwd, fv_mae_decoder_tokens_cls_fwd and
+ *      fv_mae_decoder_tokens_cls_bwd were ADDED (token assembly of the Vim MAE baseline, whose encoder carries a class token
+ *      in the middle of the kept tokens and whose decoder carries it behind the grid); no existing entry point changed. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -1128,6 +1131,41 @@ int fv_mae_decoder_tokens_fwd(const void* x, int x_dtype, const float* mask_toke
 int fv_mae_decoder_tokens_bwd(const float* dout, const int* restore_index, void* dx, int x_dtype, double* partials,
                               int n_partials, float* dmask_token, int batch, int len, int len_keep, int dim,
                               fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Token assembly with a class token (csrc/mae_tokens_cls.hip): the Vim MAE baseline.  B = batch samples, L = len grid
+ * tokens, K = len_keep kept ones, c = K / 2 the class token's place among the kept tokens; keep_index (B, K) and
+ * restore_index (B, L) int32 as fv_mae_mask_plan writes them.  x_dtype FV_F32 or FV_BF16; dim % 4 == 0; B (L + 1) < 2^31.
+ *
+ * fv_mae_encoder_tokens_cls_fwd: out (B, K + 1, dim) in x_dtype from the UN-gathered x (B, L, dim) x_dtype:
+ *   out[b, j] = x[b, keep_index[b, j]] for j < c, x[b, keep_index[b, j - 1]] for j > c (bit copies; a zero row where the
+ *   index is outside [0, L)), and out[b, c] = cls_token + pos_embed[0], added in fp32 and rounded once to x_dtype.
+ *   cls_token (dim) fp32; pos_embed fp32, of which only row 0 -- the class slot of the (L + 1, dim) table -- is read.
+ * fv_mae_encoder_tokens_cls_bwd: two launches.  dx (B, L, dim) x_dtype, EVERY row written: row l takes
+ *   dout[b, r + (r >= c)] with r = restore_index[b, l] where 0 <= r < K, zero elsewhere; dout (B, K + 1, dim) x_dtype.
+ *   dcls_token (dim) fp32 = sum over b of dout[b, c, :], added in fp64 in the order b = 0 .. B-1, rounded once.
+ * fv_mae_decoder_tokens_cls_fwd: out (B, L + 1, dim) fp32 from x (B, K + 1, dim) x_dtype:
+ *   out[b, l] = (r >= 0 ? x[b, r + (r >= c)] : mask_token rounded to x_dtype) + pos_embed[1 + l] for l < L, and
+ *   out[b, L] = x[b, c] + pos_embed[0]; mask_token (dim) fp32, pos_embed (L + 1, dim) fp32; one fp32 rounding, of the sum.
+ * fv_mae_decoder_tokens_cls_bwd: two launches, the kernels of fv_mae_decoder_tokens_bwd.  dout (B, L + 1, dim) fp32;
+ *   dx (B, K + 1, dim) x_dtype: row c takes dout[b, L], row r + (r >= c) takes dout[b, l] for the rows with r >= 0;
+ *   dmask_token (dim) fp32 = the sum of the other rows l < L (the class row is no mask row), each rounded to x_dtype first,
+ *   in fp64 in a fixed order: n_partials = ceil(B (L + 1) / FV_MAE_DECODER_ROWS_PER_BLOCK) rows of dim doubles,
+ *   caller-allocated.  restore_index must hold each of 0 .. K-1 once per sample for every row of dx to be written.
+ * No atomics, no host synchronisation: safe under stream capture; the same inputs give the same bits.
+ * Alignment: every buffer that of its element type only.
+ * ---------------------------------------------------------------------- */
+int fv_mae_encoder_tokens_cls_fwd(const void* x, int x_dtype, const float* cls_token, const float* pos_embed,
+                                  const int* keep_index, void* out, int batch, int len, int len_keep, int dim,
+                                  fv_stream_t stream);
+int fv_mae_encoder_tokens_cls_bwd(const void* dout, const int* restore_index, void* dx, int x_dtype, float* dcls_token,
+                                  int batch, int len, int len_keep, int dim, fv_stream_t stream);
+int fv_mae_decoder_tokens_cls_fwd(const void* x, int x_dtype, const float* mask_token, const float* pos_embed,
+                                  const int* restore_index, float* out, int batch, int len, int len_keep, int dim,
+                                  fv_stream_t stream);
+int fv_mae_decoder_tokens_cls_bwd(const float* dout, const int* restore_index, void* dx, int x_dtype, double* partials,
+                                  int n_partials, float* dmask_token, int batch, int len, int len_keep, int dim,
+                                  fv_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Device-side geometry of the uint8 loaders: bicubic resize, crop window and horizontal flip of decoded 8-bit images,
