@@ -50,7 +50,9 @@ def restore_training_state(snap):
 
 
 class SegmentedTrainStep:
-    """``model`` must expose ``_embed / _run_layers / _final / _head`` (fastvim_amd.fastvim.VisionMamba).
+    """``model`` must expose ``_embed / _run_layers / _final / _head``: fastvim_amd.fastvim.VisionMamba, the channel models,
+    and the un-pooled baseline fastvim_amd.vim.VisionMamba (whose ``fused_cls`` puts its class token's bookkeeping on the HIP
+    path; ``mixup`` / ``erase`` / uint8 batches as for FastVim, no ``hcs``).
     ``loss_fn(logits, target) -> scalar``.  ``x`` / ``target`` are the static input buffers the graphs read; copy
     new batches into them between steps.  ``x`` holds normalised float pixels, or -- after
     ``fastvim_amd.pixels.attach_pixel_norm(model, mean, std)`` -- the uint8 batch itself, normalised inside the patch unfold.
@@ -113,7 +115,8 @@ class SegmentedTrainStep:
         self.hcs = hcs
         if hcs is not None and "hcs" not in inspect.signature(model._embed).parameters:
             raise TypeError("SegmentedTrainStep: hcs= needs a model whose _embed takes the sampler (`_embed(x, hcs=None)`: "
-                            "fastvim_amd.models_channel_mamba_faster.VisionMamba)")
+                            "fastvim_amd.models_channel_mamba_faster.VisionMamba; fastvim.VisionMamba and vim.VisionMamba "
+                            "embed all channels)")
         if hcs is not None:
             hcs.block(x.device)                          # the index array exists before any capture
         self.exchange = flat.make_exchange(n_segments)

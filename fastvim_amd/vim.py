@@ -13,6 +13,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
+from . import vim_tokens
 from .fastvim import (Block as _FastVimBlock, DropPath, PatchEmbed as _PatchEmbed, _init_weights, segm_init_weights,
                       trunc_normal_)
 from .layernorm import RMSNorm, layer_norm_fn
@@ -60,15 +61,21 @@ def create_block(d_model, ssm_cfg=None, norm_epsilon=1e-5, drop_path=0.0, rms_no
 
 
 class VisionMamba(nn.Module):
+    # ``fused_cls`` (keyword, or set on the model): the class token's bookkeeping on the HIP path -- one launch puts it among
+    # the patch tokens and adds ``pos_embed``, the final add + norm runs on the class row alone (fastvim_amd/vim_tokens.py).
+    # Same values as the torch ops of ``forward_features``, which run while it is off (the default).
+    fused_cls = False
+
     def __init__(self, img_size=224, patch_size=16, stride=16, depth=24, embed_dim=192, channels=3,
                  num_classes=1000, ssm_cfg=None, drop_rate=0.0, drop_path_rate=0.1, norm_epsilon: float = 1e-5,
                  rms_norm: bool = True, initializer_cfg=None, fused_add_norm=False, residual_in_fp32=False,
                  device=None, dtype=None, final_pool_type="none", if_abs_pos_embed=True, if_cls_token=True,
                  init_layer_scale=None, use_middle_cls_token=True, use_norm_after_ssm=True, embed_layer=PatchEmbed,
-                 **kwargs):
+                 fused_cls=False, **kwargs):
         factory_kwargs = {"device": device, "dtype": dtype}
         kwargs.update(factory_kwargs)
         super().__init__()
+        self.fused_cls = bool(fused_cls)
         self.residual_in_fp32 = residual_in_fp32
         self.fused_add_norm = fused_add_norm
         self.final_pool_type = final_pool_type
@@ -111,7 +118,83 @@ class VisionMamba(nn.Module):
     def no_weight_decay(self):
         return {"pos_embed", "cls_token", "dist_token", "cls_token_head", "cls_token_tail"}
 
+    # forward_features in four pieces, so that a training step can be cut into segments of layers
+    # (fastvim_amd/pipeline.py::SegmentedTrainStep, as fastvim.VisionMamba offers them).  With ``fused_cls`` the class token
+    # goes in by one launch and the final norm runs on the class row alone (fastvim_amd/vim_tokens.py); without it the pieces
+    # run forward_features' own ops.
+    def _token_position(self, M):
+        return M // 2 if (self.if_cls_token and self.use_middle_cls_token) else 0
+
+    def _embed(self, x, mix=None, erase=None):
+        """``mix`` / ``erase``: a ``fastvim_amd.mixup.Mixup`` / ``fastvim_amd.erasing.RandomErasing`` whose current
+        parameters apply on the way into the patch embedding (training only: ``eval()`` paths neither mix nor erase)."""
+        B, _, H, W = x.shape
+        if not self.training:
+            mix = erase = None
+        Hg, Wg = math.ceil(H / self.patch_size), math.ceil(W / self.patch_size)
+        if self.if_abs_pos_embed and (Hg != self.token_size[0] or Wg != self.token_size[1]):
+            raise RuntimeError(f"input grid {Hg}x{Wg} differs from the model's {self.token_size}; "
+                               "build VisionMamba with the matching img_size")
+        x = self.patch_embed(x, mix=mix, erase=erase)  # (B, M, D) fp32 (conv bias added in the epilogue)
+        position = self._token_position(x.shape[1])
+        if (self.fused_cls and self.if_cls_token and self.if_abs_pos_embed
+                and vim_tokens.cls_tokens_ok(x, self.cls_token, self.pos_embed, position)):
+            x = vim_tokens.cls_tokens(x, self.cls_token, self.pos_embed, position)
+        else:
+            if self.if_cls_token:
+                x = torch.cat((x[:, :position, :], self.cls_token.expand(B, -1, -1).to(x.dtype), x[:, position:, :]), dim=1)
+            if self.if_abs_pos_embed:
+                x = x + self.pos_embed
+        if self.if_abs_pos_embed:
+            x = self.pos_drop(x)
+        if self.training:
+            DropPath.predraw([l.drop_path for l in self.layers] + [self.drop_path], x.shape[0], x.device)
+        return x, (Hg, Wg)
+
+    def _run_layers(self, hidden_states, residual, lo, hi, inference_params=None):
+        for layer_idx in range(lo, hi):
+            hidden_states, residual = self.layers[layer_idx](hidden_states, residual, inference_params=inference_params)
+        return hidden_states, residual
+
+    def _final(self, hidden_states, residual):
+        is_rms = isinstance(self.norm_f, RMSNorm)
+        token_position = self._token_position(hidden_states.shape[1] - self.num_tokens)
+        if not self.fused_add_norm:
+            residual = hidden_states if residual is None else residual + self.drop_path(hidden_states)
+            hidden_states = layer_norm_fn(residual.to(self.norm_f.weight.dtype), self.norm_f.weight, self.norm_f.bias,
+                                          eps=self.norm_f.eps, is_rms_norm=is_rms)
+        else:
+            scale = self.drop_path.row_scale(hidden_states) if isinstance(self.drop_path, DropPath) else None
+            if (self.fused_cls and self.if_cls_token
+                    and vim_tokens.add_norm_row_ok(hidden_states, residual, self.norm_f.weight, self.norm_f.bias,
+                                                   token_position, scale, self.residual_in_fp32)):
+                # the head reads the class row alone: normalise that row, and let its adjoint write the zeros of the others
+                return vim_tokens.add_norm_row(hidden_states, residual, self.norm_f.weight, self.norm_f.bias,
+                                               self.norm_f.eps, token_position, scale, is_rms, self.residual_in_fp32)
+            hidden_states = layer_norm_fn(hidden_states, self.norm_f.weight, self.norm_f.bias, eps=self.norm_f.eps,
+                                          residual=residual, prenorm=False, residual_in_fp32=self.residual_in_fp32,
+                                          is_rms_norm=is_rms, row_scale=scale)
+        if self.if_cls_token:
+            return hidden_states[:, token_position, :]
+        if self.final_pool_type == "none":
+            return hidden_states[:, -1, :]
+        elif self.final_pool_type == "mean":
+            return hidden_states.mean(dim=1)
+        elif self.final_pool_type in ("max", "all"):
+            return hidden_states
+        raise NotImplementedError
+
+    def _head(self, x):
+        x = probe_head_forward(self.head, x) if (is_probe_head(self.head) and x.is_cuda) else linear_module(self.head, x)
+        if self.final_pool_type == "max":
+            x = x.max(dim=1)[0]
+        return x
+
     def forward_features(self, x, inference_params=None, out_indices=None):
+        if self.fused_cls and out_indices is None:
+            hidden_states, _ = self._embed(x)
+            hidden_states, residual = self._run_layers(hidden_states, None, 0, len(self.layers), inference_params)
+            return self._final(hidden_states, residual)
         B, _, H, W = x.shape
         x = self.patch_embed(x)                        # (B, M, D) fp32 (conv bias added in the epilogue)
         M = x.shape[1]
@@ -166,10 +249,7 @@ class VisionMamba(nn.Module):
         x = self.forward_features(x, inference_params)
         if return_features:
             return x
-        x = probe_head_forward(self.head, x) if (is_probe_head(self.head) and x.is_cuda) else linear_module(self.head, x)
-        if self.final_pool_type == "max":
-            x = x.max(dim=1)[0]
-        return x
+        return self._head(x)
 
 
 class MM_Vim(VisionMamba):

@@ -105,7 +105,11 @@ const char* fv_last_error(void);
  *      FV_GEMM_GROUPED_*); no existing entry point changed and every shape runs on the kernel it ran on.
  *      Later, still 3: fv_mae_encoder_tokens_cls_fwd, fv_mae_encoder_tokens_cls_bwd, fv_mae_decoder_tokens_cls_fwd and
  *      fv_mae_decoder_tokens_cls_bwd were ADDED (token assembly of the Vim MAE baseline, whose encoder carries a class token
- *      in the middle of the kept tokens and whose decoder carries it behind the grid); no existing entry point changed. */
+ *      in the middle of the kept tokens and whose decoder carries it behind the grid); no existing entry point changed.
+ *      Later, still 3: fv_vim_cls_tokens_fwd, fv_vim_cls_tokens_bwd, fv_add_norm_row_fwd and fv_add_norm_row_bwd were ADDED
+ *      (the supervised Vim baseline: its class token put among the patch tokens with the position table, and its final
+ *      add + norm of the class row alone); no existing entry point changed -- fv_add_norm_fwd / _bwd run the kernels they
+ *      ran, whose bodies the row forms share. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -1166,6 +1170,46 @@ int fv_mae_decoder_tokens_cls_fwd(const void* x, int x_dtype, const float* mask_
 int fv_mae_decoder_tokens_cls_bwd(const float* dout, const int* restore_index, void* dx, int x_dtype, double* partials,
                                   int n_partials, float* dmask_token, int batch, int len, int len_keep, int dim,
                                   fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * The class token of the supervised Vim baseline (csrc/vim_tokens.hip, csrc/norm.hip): B = batch samples, M = len patch
+ * tokens, p = position of the class token among the M + 1 rows (0 <= p <= M).  y_dtype FV_F32 or FV_BF16; dim % 4 == 0;
+ * B (M + 1) < 2^31.
+ *
+ * fv_vim_cls_tokens_fwd: out (B, M + 1, dim) fp32 from y (B, M, dim) y_dtype, the patch projection:
+ *   out[b, j] = (j == p ? cls_token rounded to y_dtype : y[b, j - (j > p)]) + pos_embed[j], ONE fp32 add -- the values of
+ *   `cat((x[:, :p], cls_token.expand(B, -1, -1).to(x.dtype), x[:, p:]), 1) + pos_embed`.  cls_token (dim) fp32,
+ *   pos_embed (M + 1, dim) fp32.  A thread moves 16 bytes of y (8 for bf16 when dim % 8 != 0).
+ * fv_vim_cls_tokens_bwd: ONE launch, one thread per (row j, vector of channels) walking b = 0 .. B-1.  dout (B, M + 1, dim)
+ *   fp32; dy (B, M, dim) y_dtype: dy[b, i] = dout[b, i + (i >= p)] rounded to y_dtype (fp32: a bit copy);
+ *   dpos_embed (M + 1, dim) fp32 = sum over b of dout[b, j, :], added in fp64 in that order, rounded once;
+ *   dcls_token (dim) fp32 = the same sum of row p with every term rounded to y_dtype first (fp32: dpos_embed[p]).
+ *
+ * fv_add_norm_row_fwd: fv_add_norm_fwd of row `position` of every sample and of no other row.  hidden / residual
+ *   (B, rows, N); row_scale (B) fp32 or NULL, one factor per sample; y (B, N), residual_out (B, N) -- the normalised
+ *   input, which the backward reads -- mean (B, NULL for RMSNorm) and rstd (B) are packed.  The kernel bodies are those of
+ *   fv_add_norm_fwd, chosen by N the same way: y, residual_out, mean and rstd equal that launch's rows b * rows + position
+ *   bit for bit.
+ * fv_add_norm_row_bwd: ONE launch writes ALL of dhidden and dresidual (B, rows, N) (dresidual may be NULL): row `position`
+ *   of each sample from the norm's adjoint -- bit for bit the rows fv_add_norm_bwd writes for a dy that is zero outside
+ *   those rows -- and zero everywhere else.  dy (B, N), r (B, N) = residual_out, mean, rstd as the forward left them.
+ *   partial_dw / partial_db: (fv_add_norm_blocks(B), N) fp32, fixed-order sums over the B rows (reduce with
+ *   fv_reduce_partials); partial_db NULL without a bias.
+ * No atomics, no host synchronisation: safe under stream capture; the same inputs give the same bits.
+ * Alignment: fv_vim_cls_tokens_*: every buffer that of its element type only; fv_add_norm_row_*: as fv_add_norm_*.
+ * ---------------------------------------------------------------------- */
+int fv_vim_cls_tokens_fwd(const void* y, int y_dtype, const float* cls_token, const float* pos_embed, float* out, int batch,
+                          int len, int dim, int position, fv_stream_t stream);
+int fv_vim_cls_tokens_bwd(const float* dout, void* dy, int y_dtype, float* dpos_embed, float* dcls_token, int batch, int len,
+                          int dim, int position, fv_stream_t stream);
+int fv_add_norm_row_fwd(const void* hidden, int hidden_dtype, const void* residual, int residual_dtype, const float* weight,
+                        const float* bias, const float* row_scale, void* y, int y_dtype, void* residual_out,
+                        int residual_out_dtype, float* mean, float* rstd, int batch, int rows, int position, int N, float eps,
+                        int is_rms_norm, fv_stream_t stream);
+int fv_add_norm_row_bwd(const void* dy, int dy_dtype, const void* r, int r_dtype, const float* weight, const float* mean,
+                        const float* rstd, const float* row_scale, void* dhidden, int dhidden_dtype, void* dresidual,
+                        int dresidual_dtype, float* partial_dw, float* partial_db, int batch, int rows, int position, int N,
+                        int is_rms_norm, fv_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Device-side geometry of the uint8 loaders: bicubic resize, crop window and horizontal flip of decoded 8-bit images,
