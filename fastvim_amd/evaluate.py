@@ -14,13 +14,13 @@ quote are ``val_acc_ema``.  Here:
   batch of an epoch replays the same graph.
 """
 import contextlib
-import warnings
 
 import torch
 import torch.distributed as dist
 
 from . import _lib as L
 from ._devblock import BlockWriter
+from .graph_chain import capture, capture_allowed, capture_mode, warm_up
 
 ACC_HEAD = 3             # include/fastvim_hip.h, FV_EVAL_ACC_HEAD: [loss_sum (fp64) | n_seen | n_correct] before the class counters
 MAX_CLASSES = 2048       # the row kernel keeps a row in one wave's registers (csrc/ce_row.h: 64 lanes x 32)
@@ -223,21 +223,14 @@ class ValidationStep:
         cpu_rng, gpu_rng = torch.get_rng_state(), torch.cuda.get_rng_state(dev)
         with _eval_mode(model):
             # the first forward tells the number of classes; it and the warm-up steps run on a side stream, as a capture
-            # wants, and what they add to the metrics is zeroed again
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                classes = self._forward().shape[1]
+            # wants (with use_graph=False too), and what they add to the metrics is zeroed again
+            classes = warm_up(self._forward, 1, dev).shape[1]
             self.live = EvalMetrics(classes, dev)
             self.live.scratch(self.batch)
             if self.ema:
                 self.ema_metrics = EvalMetrics(classes, dev)
                 self.ema_metrics.scratch(self.batch)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(max(int(warmup), 1) if use_graph else int(warmup)):
-                    self._sequence()
-            torch.cuda.current_stream(dev).wait_stream(side)
+            warm_up(self._sequence, max(int(warmup), 1) if use_graph else int(warmup), dev)
             self.reset()
             torch.cuda.synchronize(dev)
             if use_graph:
@@ -257,19 +250,10 @@ class ValidationStep:
                 self.ema_metrics.accumulate(self._forward(), self.labels, self._nv)
 
     def _capture(self):
-        from . import graph_capture_safe
-        if not graph_capture_safe():
-            warnings.warn("ValidationStep: HIP was initialised before `import fastvim_amd` could switch graph packet capture "
-                          "off (DESIGN.md section 5) -- running this step EAGERLY instead.  Import fastvim_amd first to get "
-                          "graph replay.", RuntimeWarning, stacklevel=3)
+        if not capture_allowed("ValidationStep"):
             self.use_graph = False
             return
-        # (a process group's watchdog thread may query events while this thread captures: pipeline.py, _capture)
-        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=torch.cuda.graph_pool_handle(), capture_error_mode=mode):
-            self._sequence()
-        self.graph = g
+        self.graph, _ = capture(torch.cuda.graph_pool_handle(), capture_mode(), self._sequence)
 
     # ------------------------------------------------------------------ run
     def step(self, n_valid=None):

@@ -19,8 +19,6 @@ The recipe's learning-rate schedule (linear_imagenet.py:118-130), set between st
         min_lr + (base_lr - min_lr) * 0.5 * (1 + math.cos(math.pi * (epoch - warmup_epochs) / (epochs - warmup_epochs)))
     opt.set_lr(lr); x.copy_(images); labels.copy_(targets); loss = step.step()
 """
-import warnings
-
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -28,6 +26,7 @@ import torch.nn as nn
 from . import _lib as L
 from .gemm import gemm_any_nn, gemm_any_nt
 from .glue_ops import column_sum
+from .graph_chain import capture, capture_allowed, capture_mode, restore_training_state, snapshot_training_state, warm_up
 from .losses import CrossEntropyLoss
 from .mamba_simple_faster import _compute_dtype, _direct_grad, _shadow, _wgrad
 
@@ -373,61 +372,24 @@ class LinearProbeStep:
         return loss
 
     # ------------------------------------------------------------------ capture / run
-    def _snapshot(self):
-        f, o = self.flat, self.opt
-        bufs = [f.param_flat, f.shadow_flat]
-        bufs += [b for b in (self.bn.running_mean, self.bn.running_var, self.bn.num_batches_tracked) if b is not None]
-        for v in vars(o).values():
-            if torch.is_tensor(v) and v.is_cuda and all(v is not b for b in bufs):
-                bufs.append(v)
-        dev = f.param_flat.device
-        return [(b, b.clone()) for b in bufs], torch.get_rng_state(), torch.cuda.get_rng_state(dev), dev
-
-    def _restore(self, snap):
-        bufs, cpu_rng, gpu_rng, dev = snap
-        with torch.no_grad():
-            for b, saved in bufs:
-                b.copy_(saved)
-        torch.set_rng_state(cpu_rng)
-        torch.cuda.set_rng_state(gpu_rng, dev)
-
     def _capture(self, warmup):
-        from . import graph_capture_safe
-        if not graph_capture_safe():
-            warnings.warn("LinearProbeStep: HIP was initialised before `import fastvim_amd` could switch graph packet capture "
-                          "off (DESIGN.md section 5) -- running this step EAGERLY instead.  Import fastvim_amd first to get "
-                          "graph replay.", RuntimeWarning, stacklevel=3)
+        if not capture_allowed("LinearProbeStep"):
             self.use_graph = False
             return
-        snap = self._snapshot()
-        pool = torch.cuda.graph_pool_handle()
-        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._eager_step()
-        torch.cuda.current_stream().wait_stream(side)
+        bn = self.bn
+        snap = snapshot_training_state(self.flat, self.opt, extra=[b for b in (bn.running_mean, bn.running_var,
+                                                                                bn.num_batches_tracked) if b is not None])
+        pool, mode = torch.cuda.graph_pool_handle(), capture_mode()
+        warm_up(self._eager_step, warmup)
+        restore_training_state(snap)
         torch.cuda.synchronize()
-        self._restore(snap)
-        torch.cuda.synchronize()
-
-        def graph(*pieces):
-            g = torch.cuda.CUDAGraph()
-            out = None
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=mode):
-                for piece in pieces:
-                    r = piece()
-                    out = r if r is not None else out
-            return g, out
-
         if not self.sync:
-            g, self.loss = graph(self._features, self._head, self._optimize)
+            g, self.loss = capture(pool, mode, self._features, self._head, self._optimize)
             self.graphs = (g,)
         else:
-            g0, _ = graph(self._features)
-            g1, self.loss = graph(self._head)
-            g2, _ = graph(self._optimize)
+            g0, _ = capture(pool, mode, self._features)
+            g1, self.loss = capture(pool, mode, self._head)
+            g2, _ = capture(pool, mode, self._optimize)
             self.graphs = (g0, g1, g2)
 
     def step(self):

@@ -21,18 +21,15 @@ key block when it RUNS, so the caller draws between micro-batches, like ``opt.se
 
     x.copy_(imgs, non_blocking=True); sampler.sample(); loss = step.micro_step()
 """
-import warnings
-
 import torch
-import torch.distributed as dist
 
 from . import mae_tokens
-from .pipeline import restore_training_state, snapshot_training_state
+from .graph_chain import ChainStep
 
 _PROTOCOL = ("_embed_masked", "_run_layers", "_tail")
 
 
-class MAEPretrainStep:
+class MAEPretrainStep(ChainStep):
     """``model``: a ``fastvim_amd.models_mae.MaskedAutoencoderViM`` in training mode (``_embed_masked / _run_layers / _tail``;
     a model without them -- the un-pooled ``fastvim_amd.fastvim_mae`` class -- raises ``TypeError``).  ``x``: the static image
     buffer the graphs read, normalised float pixels or, after ``fastvim_amd.pixels.attach_pixel_norm``, the uint8 batch.
@@ -64,107 +61,37 @@ class MAEPretrainStep:
             raise ValueError(f"MAEPretrainStep: the masking plan does not serve batch {tuple(x.shape)}, token grid {grid}, "
                              f"len_keep {len_keep} (mae_tokens.plan_shape_ok: at most {mae_tokens.MAX_TOKENS} tokens, at "
                              f"least {mae_tokens.MIN_KEEP} kept)")
-        self.model, self.flat, self.opt, self.x, self.sampler = model, flat, opt, x, sampler
+        self.model, self.sampler = model, sampler
         self.mask_ratio, self.accum_iter, self.amp_dtype = float(mask_ratio), int(accum_iter), amp_dtype
         sampler.block(x.device)                          # the key block exists before any capture
-        self.exchange = flat.make_exchange(n_segments)
-        self.runs = self.exchange.layers                 # (lo, hi) block ranges in BACKWARD order
-        self.K = len(self.runs)
-        self._gscale = 1.0 / (self.accum_iter * self.exchange.world_size)
-        self.use_graph = use_graph
-        self.loss = self.mask = None
+        super().__init__(flat, opt, x, n_segments, use_graph, accum_iter=self.accum_iter)
+        self.mask = None
         self.optimizer_ran = False
         self._micro = 0                                  # position inside the group of accum_iter micro-batches
-        self._seed = torch.ones((), device=x.device, dtype=torch.float32)      # d loss / d loss, allocated once outside the graphs
-        self._cuts = None
-        self.graphs = None
         if use_graph:
             self._capture(warmup)
 
     # ------------------------------------------------------------------ the pieces
     def _forward(self):
-        m = self.model
-        embed_masked, run_layers, tail = (getattr(m, name) for name in self._protocol)
-        cuts = []              # per run in FORWARD order: (inputs (leaves) or None, outputs)
+        embed_masked, run_layers, tail = (getattr(self.model, name) for name in self._protocol)
         with torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.amp_dtype != torch.float32):
             h, plan = embed_masked(self.x, self.mask_ratio, self.sampler)
-            res = None
-            for i, (lo, hi) in enumerate(self.runs[::-1]):
-                if i > 0:          # cut: this run's inputs are leaves that alias the previous run's outputs
-                    h, res = h.detach().requires_grad_(), res.detach().requires_grad_()
-                    ins = (h, res)
-                else:
-                    ins = None
-                h, res = run_layers(h, res, lo, hi, plan)
-                cuts.append([ins, (h, res)])
-            loss, _ = tail(h, res, self.x, plan)
-        cuts[-1][1] = (loss,)
-        self._cuts = cuts
+            h, res = self._run_cuts(lambda lo, hi, h, res: run_layers(h, res, lo, hi, plan), (h, None))
+            loss, _ = tail(h, res, self.x, plan)      # (graph 0 of the backward chain also holds the decoder and the loss)
         self.mask = plan.mask
-        return loss.detach()
-
-    def _backward(self, k):
-        """Backward of run k (backward order: k = 0 is the decoder, the loss and the last run of encoder blocks)."""
-        i = self.K - 1 - k                      # forward index
-        outs = self._cuts[i][1]
-        if k == 0:
-            torch.autograd.backward(outs[0], self._seed if outs[0].dtype == self._seed.dtype else None)
-        else:
-            nxt = self._cuts[i + 1][0]
-            torch.autograd.backward(list(outs), [t.grad for t in nxt])
-        self.flat.finish_backward()             # this run's queued weight-gradient GEMMs and partial sums
-        self._cuts[i][1] = None                 # free the run's autograd graph
+        return self._end_forward(loss)
 
     # ------------------------------------------------------------------ capture / run
-    def _eager_micro(self, last):
-        loss = self._forward()
-        for k in range(self.K):
-            self._backward(k)
-            if last:
-                self.exchange.launch(k)
-        if last:
-            self.exchange.finish(mean=False)     # sums: the optimizer kernel applies 1 / (accum_iter world) as it reads them
-            self.opt.step(grad_scale=self._gscale)
-        return loss
+    def _snapshot(self):
+        return (*super()._snapshot(), self.sampler.last()[1])
 
-    def _capture(self, warmup):
-        from . import graph_capture_safe
-        if not graph_capture_safe():
-            # known to replay some captured steps wrongly (non-finite after a few replays): do not capture at all
-            warnings.warn("MAEPretrainStep: HIP was initialised before `import fastvim_amd` could switch graph packet capture "
-                          "off (DEBUG_CLR_GRAPH_PACKET_CAPTURE=0): on ROCm 7.2 some captured training steps replay wrongly "
-                          "(DESIGN.md section 5) -- running this step EAGERLY instead.  Import fastvim_amd first, or export "
-                          "the variable, to get graph replay.", RuntimeWarning, stacklevel=3)
-            self.use_graph = False
-            return
-        snap, counter = snapshot_training_state(self.flat, self.opt), self.sampler.last()[1]
-        pool = torch.cuda.graph_pool_handle()
-        # (a live process group's watchdog thread polls events: "thread_local" keeps that legal during capture, pipeline.py)
-        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):              # whole steps: allocator, lazily built buffers, RCCL communicators
-                self.flat.zero_grad()
-                self._eager_micro(True)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        restore_training_state(snap)
-        self.sampler.set_counter(counter)
-        torch.cuda.synchronize()
-        g_fwd = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g_fwd, pool=pool, capture_error_mode=mode):
-            self.loss = self._forward()
-        g_bwd = []
-        for k in range(self.K):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=mode):
-                self._backward(k)
-            g_bwd.append(g)
-        g_opt = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g_opt, pool=pool, capture_error_mode=mode):
-            self.opt.step(grad_scale=self._gscale)
-        self.graphs = (g_fwd, g_bwd, g_opt)
+    def _restore(self, snap):
+        super()._restore(snap)
+        self.sampler.set_counter(snap[4])
+
+    def _warm_step(self):                    # a whole step: a group of one micro-batch
+        self.flat.zero_grad()
+        self._eager()
 
     def micro_step(self):
         """One micro-batch on what ``x`` holds, with the masks of the sampler's last ``sample()``: forward and backward into
@@ -174,17 +101,9 @@ class MAEPretrainStep:
         if self._micro == 0:
             self.flat.zero_grad()
         if not self.use_graph:
-            self.loss = self._eager_micro(last)
+            self.loss = self._eager(last)
         else:
-            g_fwd, g_bwd, g_opt = self.graphs
-            g_fwd.replay()
-            for k in range(self.K):
-                g_bwd[k].replay()
-                if last:
-                    self.exchange.launch(k)
-            if last:
-                self.exchange.finish(mean=False)
-                g_opt.replay()
+            self._replay(last)
         self._micro = 0 if last else self._micro + 1
         self.optimizer_ran = last
         return self.loss

@@ -16,40 +16,21 @@ backward of run k is ``torch.autograd.backward(outputs_k, grads of run k+1's inp
 exchanged and the chain computes what the single-graph step computes: bit for bit with ``gemm.FILL = False``; with
 the shipped default (``gemm.fill_splits`` re-cuts a segment's smaller weight-gradient groups into more K slices) the
 same sums are taken in another order and the two agree to rounding (tests/test_pipeline_gpu.py asserts both).
+
+How the chain is captured and in what order it runs -- the capture mode under a live process group (the watchdog thread), the
+warm-up, the cuts, the backward of a run -- is fastvim_amd/graph_chain.py, shared with the MAE pre-training step.
 """
+import contextlib
 import inspect
 import warnings
 
 import torch
-import torch.distributed as dist
 
 from . import pixels
+from .graph_chain import ChainStep, restore_training_state, snapshot_training_state      # noqa: F401  (both re-exported)
 
 
-def snapshot_training_state(flat, opt):
-    """What the warm-up steps of a capture may advance, cloned: (buffers, CPU RNG state, GPU RNG state, device) for
-    ``restore_training_state`` (``SegmentedTrainStep`` and ``fastvim_amd.mae_step.MAEPretrainStep``)."""
-    f, o = flat, opt
-    # every tensor attribute of the optimizer (moments, EMA, step count, lr, decay mask, ...) and the state's own buffers:
-    # whatever a warm-up step may advance is put back, not a hand-picked list
-    bufs = [f.param_flat, f.shadow_flat] + list(getattr(f, "_t_dst", [])) + list(getattr(f, "_tx_dst", [])) + list(getattr(f, "_pk_dst", []))   # (+ the transposed in_proj / x_proj shadows and the fragment-major copies)
-    for v in vars(o).values():
-        if torch.is_tensor(v) and v.is_cuda and all(v is not b for b in bufs):
-            bufs.append(v)
-    dev = f.param_flat.device
-    return [(b, b.clone()) for b in bufs], torch.get_rng_state(), torch.cuda.get_rng_state(dev), dev
-
-
-def restore_training_state(snap):
-    bufs, cpu_rng, gpu_rng, dev = snap
-    with torch.no_grad():
-        for b, saved in bufs:
-            b.copy_(saved)
-    torch.set_rng_state(cpu_rng)
-    torch.cuda.set_rng_state(gpu_rng, dev)
-
-
-class SegmentedTrainStep:
+class SegmentedTrainStep(ChainStep):
     """``model`` must expose ``_embed / _run_layers / _final / _head``: fastvim_amd.fastvim.VisionMamba, the channel models,
     and the un-pooled baseline fastvim_amd.vim.VisionMamba (whose ``fused_cls`` puts its class token's bookkeeping on the HIP
     path; ``mixup`` / ``erase`` / uint8 batches as for FastVim, no ``hcs``).
@@ -85,8 +66,7 @@ class SegmentedTrainStep:
         if erase is not None and hcs is not None:
             raise ValueError("SegmentedTrainStep: erase= and hcs= do not combine (the channel recipes of the reference do not "
                              "erase, and the per-channel unfold has no erase form)")
-        self.model, self.flat, self.opt, self.loss_fn = model, flat, opt, loss_fn
-        self.x, self.target, self.amp_dtype = x, target, amp_dtype
+        self.model, self.loss_fn, self.target, self.amp_dtype = model, loss_fn, target, amp_dtype
         # batch-mode Mixup / CutMix inside the step: the images are mixed on their way into the patch embedding by whatever
         # the Mixup's device block holds when the graph RUNS -- the caller calls mixup.sample() between steps, the step never
         # does -- and `target` is the (B,) int64 label buffer that mixup.criterion() turns into the soft target
@@ -119,16 +99,8 @@ class SegmentedTrainStep:
                             "embed all channels)")
         if hcs is not None:
             hcs.block(x.device)                          # the index array exists before any capture
-        self.exchange = flat.make_exchange(n_segments)
-        self.runs = self.exchange.layers                 # (lo, hi) block ranges in BACKWARD order
-        self.K = len(self.runs)
-        self._gscale = 1.0 / self.exchange.world_size
-        self.use_graph = use_graph
-        self.loss = None
-        self._seed = torch.ones((), device=x.device, dtype=torch.float32)      # d loss / d loss, allocated once outside the graphs
-        self._cuts = None
+        super().__init__(flat, opt, x, n_segments, use_graph)
         self._exposed = []                               # (event before finish, event after) of the timed steps
-        self.graphs = None
         self.families = None                             # with hcs: {count: (forward graph, backward graphs, loss tensor)}
         if use_graph:
             pe = getattr(model, "patch_embed", None)
@@ -143,7 +115,6 @@ class SegmentedTrainStep:
     def _forward(self):
         m = self.model
         self.flat.zero_grad()
-        cuts = []              # per run in FORWARD order: (inputs (leaves) or None, outputs)
         with torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.amp_dtype != torch.float32):
             kw = {} if self.hcs is None else {"hcs": self.hcs}
             x = self.x
@@ -159,142 +130,62 @@ class SegmentedTrainStep:
             else:              # (the channel models: the whole image is mixed before channels are selected, the reference's order)
                 xin = pixels.normalise_like(m, x) if x.dtype == torch.uint8 else x
                 h, _ = m._embed(self.mixup.mix_batch(xin, out=self._x_mixed), **kw)
-            res, pend = None, None
-            fwd_runs = self.runs[::-1]
             open_runs = hasattr(m, "_run_layers_open")
-            for i, (lo, hi) in enumerate(fwd_runs):
-                if i > 0:          # cut: this run's inputs are leaves that alias the previous run's outputs
-                    res = res.detach().requires_grad_()
-                    if pend is not None:      # the chain of fused blocks continues across the cut (fastvim._run_layers_open):
-                        pend = (pend[0].detach().requires_grad_(), pend[1])      # its hand-over is the gated activations
-                        ins = (pend[0], res)
-                    else:
-                        h = h.detach().requires_grad_()
-                        ins = (h, res)
-                else:
-                    ins = None
-                if open_runs:
-                    h, res, pend = m._run_layers_open(h, res, lo, hi, pend=pend)
-                else:
-                    h, res = m._run_layers(h, res, lo, hi)
-                cuts.append([ins, (h if pend is None else pend[0], res)])
-            if pend is not None:
-                h = m._close_run(pend)
-            logits = m._head(m._final(h, res))
-        loss = self.loss_fn(logits, self.target)
-        cuts[-1][1] = (loss,)
-        self._cuts = cuts
-        return loss.detach()
 
-    def _backward(self, k):
-        """Backward of run k (backward order: k = 0 is the last run of blocks + head + loss)."""
-        i = self.K - 1 - k                      # forward index
-        outs = self._cuts[i][1]
-        if k == 0:
-            seed = self._seed if (outs[0].dim() == 0 and outs[0].dtype == self._seed.dtype and outs[0].device == self._seed.device) else None
-            torch.autograd.backward(outs[0], seed)      # (the seed autograd would otherwise fill inside the captured graph)
-        else:
-            nxt = self._cuts[i + 1][0]
-            torch.autograd.backward(list(outs), [t.grad for t in nxt])
-        self.flat.finish_backward()             # this run's queued weight-gradient GEMMs and partial sums
-        self._cuts[i][1] = None                 # free the run's autograd graph
+            def run(lo, hi, a, res, w=None):
+                # w: the chain of fused blocks continues across the cut (fastvim._run_layers_open) -- the weight of its
+                # pending out_proj; `a`, the activation that crosses the cut, is then the gated one and not the hidden state
+                if not open_runs:
+                    return m._run_layers(a, res, lo, hi)
+                h, res, pend = m._run_layers_open(a if w is None else None, res, lo, hi, pend=None if w is None else (a, w))
+                return (h, res) if pend is None else (pend[0], res, pend[1])
+
+            h, res, *w = self._run_cuts(run, (h, None))
+            if w:
+                h = m._close_run((h, w[0]))
+            logits = m._head(m._final(h, res))
+        return self._end_forward(self.loss_fn(logits, self.target))
 
     # ------------------------------------------------------------------ capture / run
-    def _eager_step(self):
-        loss = self._forward()
-        for k in range(self.K):
-            self._backward(k)
-            self.exchange.launch(k)
-        self.exchange.finish(mean=False)         # sums: the optimizer kernel applies 1 / world as it reads the gradient
-        self.opt.step(grad_scale=self._gscale)
-        return loss
-
     def _snapshot(self):
         return (*snapshot_training_state(self.flat, self.opt), None if self.hcs is None else self.hcs.last())
 
-    def _restore(self, snap, sampler=True):
+    def _restore(self, snap):
         restore_training_state(snap[:4])
-        subset = snap[4]
-        if subset is not None and sampler:
-            self.hcs.set(subset)
+        if snap[4] is not None:
+            self.hcs.set(snap[4])
 
-    def _capture(self, warmup):
-        from . import graph_capture_safe
-        if not graph_capture_safe():
-            # known to replay some captured steps wrongly (non-finite after a few replays): do not capture at all
-            warnings.warn("SegmentedTrainStep: HIP was initialised before `import fastvim_amd` could switch graph packet "
-                          "capture off (DEBUG_CLR_GRAPH_PACKET_CAPTURE=0): on ROCm 7.2 some captured training steps replay "
-                          "wrongly (DESIGN.md section 5) -- running this step EAGERLY instead.  Import fastvim_amd first, or "
-                          "export the variable, to get graph replay.", RuntimeWarning, stacklevel=3)
-            self.use_graph = False
-            return
-        snap = self._snapshot()
-        pool = torch.cuda.graph_pool_handle()
-        # With a process group alive, its watchdog THREAD polls the events of finished collectives (hipEventQuery); under the
-        # default "global" capture mode any thread's event query while this thread captures is an error
-        # (hipErrorStreamCaptureUnsupported: "operation not permitted when stream is capturing" -- it took the whole process
-        # down, intermittently, in tests/test_pipeline_gpu.py::test_rccl_buckets_between_backward_graphs).  "thread_local"
-        # restricts the check to the capturing thread, which issues nothing but kernel launches.
-        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-
-        def family():
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    self._eager_step()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self._restore(snap, sampler=False)           # (a family keeps the subset it was warmed up with for its capture)
-            torch.cuda.synchronize()
-            g_fwd = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_fwd, pool=pool, capture_error_mode=mode):
-                loss = self._forward()
-            g_bwd = []
-            for k in range(self.K):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, capture_error_mode=mode):
-                    self._backward(k)
-                g_bwd.append(g)
-            return g_fwd, g_bwd, loss
-
+    def _capture_families(self, warmup, snap, pool, mode):
+        own, snap = snap[4], (*snap[:4], None)           # (a family keeps the subset it was warmed up with for its capture)
         if self.hcs is None:
-            g_fwd, g_bwd, self.loss = family()
-        else:
-            # one family per channel count, the largest first (it sizes the shared pool); each is warmed up and captured with
-            # the first c channels in the array -- a replay reads whatever the array holds then
-            self.families = {}
-            for c in range(self.hcs.num_channels, 0, -1):
-                self.hcs.set(range(c))
-                self.families[c] = family()
-            self.hcs.set(snap[4])                        # the sampler's own selection again
-            g_fwd, g_bwd, self.loss = self.families[self.hcs.count]
-        g_opt = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g_opt, pool=pool, capture_error_mode=mode):
-            self.opt.step(grad_scale=self._gscale)
-        self.graphs = (g_fwd, g_bwd, g_opt)
+            return self._capture_family(warmup, snap, pool, mode)
+        # one family per channel count, the largest first (it sizes the shared pool); each is warmed up and captured with
+        # the first c channels in the array -- a replay reads whatever the array holds then
+        self.families = {}
+        for c in range(self.hcs.num_channels, 0, -1):
+            self.hcs.set(range(c))
+            self.families[c] = self._capture_family(warmup, snap, pool, mode)
+        self.hcs.set(own)                                # the sampler's own selection again
+        return self.families[self.hcs.count]
+
+    @contextlib.contextmanager
+    def _time_exposed(self):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        yield
+        e1.record()
+        self._exposed.append((e0, e1))
 
     def step(self, time_exposed=False):
         """One training step; returns the (device) loss tensor.  ``time_exposed`` brackets the wait for the gradient
         exchange with events (read them with ``exposed_ms()`` after a synchronize)."""
         if not self.use_graph:
-            self.loss = self._eager_step()
+            self.loss = self._eager()
             return self.loss
-        g_fwd, g_bwd, g_opt = self.graphs
         if self.families is not None:                    # the family of the sampler's current count
             g_fwd, g_bwd, self.loss = self.families[self.hcs.count]
-        g_fwd.replay()
-        for k in range(self.K):
-            g_bwd[k].replay()
-            self.exchange.launch(k)
-        if time_exposed:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        self.exchange.finish(mean=False)
-        if time_exposed:
-            e1.record()
-            self._exposed.append((e0, e1))
-        g_opt.replay()
+            self.graphs = (g_fwd, g_bwd, self.graphs[2])
+        self._replay(time_exposed=self._time_exposed if time_exposed else None)
         return self.loss
 
     def exposed_ms(self):
