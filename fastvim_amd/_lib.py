@@ -53,6 +53,7 @@ C_ABI_SYMBOLS = (
     "fv_gemm_bf16_plan", "fv_gemm_bf16_tn_grouped_plan",
     "fv_mae_encoder_tokens_cls_fwd", "fv_mae_encoder_tokens_cls_bwd", "fv_mae_decoder_tokens_cls_fwd", "fv_mae_decoder_tokens_cls_bwd",
     "fv_vim_cls_tokens_fwd", "fv_vim_cls_tokens_bwd", "fv_add_norm_row_fwd", "fv_add_norm_row_bwd",
+    "fv_chan_cls_tokens_fwd", "fv_chan_cls_tokens_bwd",
 )
 
 

@@ -467,10 +467,19 @@ class FlatAdamW:
       gradient -- what Lightning clips under DDP -- and every rank computes it from the same all-reduced buffer, so no
       collective is added.
     * ``skip_nonfinite``: a step whose gradient norm is not finite changes nothing (parameters, moments, EMA, shadow,
-      step count) and is counted in ``last_stats()["skipped_steps"]``."""
+      step count) and is counted in ``last_stats()["skipped_steps"]``.
+
+    A weight-decay SCHEDULE (every cell-imaging recipe: cell_imaging/supervised.py:117-120 writes a cosine from
+    ``weight_decay`` to ``weight_decay_end`` into the first parameter group before each step) is ``set_weight_decay(wd)``
+    between steps, next to ``set_lr``.  In ``fv_adamw_flat`` the decay is a kernel ARGUMENT, which a captured graph would
+    replay as captured; the schedule therefore needs the grouped kernel, whose ``(lr_scale, weight_decay)`` rows are device
+    memory.  ``scheduled_weight_decay=True`` selects it for an optimizer that has none of the three arguments above (two
+    groups, from ``weight_decay`` and ``no_decay``: the same update as the un-grouped kernel computes with that value --
+    tests/test_optim_groups_gpu.py); without it, and without those arguments, the object launches ``fv_adamw_flat`` as it
+    always did and ``set_weight_decay`` raises."""
 
     def __init__(self, flat, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, no_decay=(),
-                 ema_decay=None, param_groups=None, max_grad_norm=None, skip_nonfinite=False):
+                 ema_decay=None, param_groups=None, max_grad_norm=None, skip_nonfinite=False, scheduled_weight_decay=False):
         self.flat = flat
         dev = flat.param_flat.device
         n = flat.param_flat.numel()
@@ -483,9 +492,11 @@ class FlatAdamW:
         self.step_t = torch.zeros(1, device=dev, dtype=torch.float32)
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
         self.skip_nonfinite = bool(skip_nonfinite)
-        self._grouped = param_groups is not None or max_grad_norm is not None or self.skip_nonfinite
+        self._grouped = (param_groups is not None or max_grad_norm is not None or self.skip_nonfinite
+                         or bool(scheduled_weight_decay))
         self.group_ids = self.group_table = self.max_norm = self.partials = self.stats = None
         self._group_row_of = None
+        self._decay_names = self._decay_rows = None      # the schedule's rows (``set_weight_decay``): grouped mode only
         self.decay_mask = None
         if not self._grouped:
             mask = torch.zeros(n, dtype=torch.uint8)
@@ -534,9 +545,41 @@ class FlatAdamW:
             self._group_table_full[:len(table)].copy_(torch.tensor(table, dtype=torch.float32).view(-1, 2))
         self._group_row_of = {nm: rows[key] for nm, key in per_name.items()}
         self.group_table = self._group_table_full[:len(table)]     # (rows, 2) view: (lr_scale, weight_decay), writable
+        # the rows a weight-decay schedule writes: those of the parameters that were decayed AT CONSTRUCTION (a later call
+        # -- load_state_dict -- re-draws the rows, not the set).  A row that holds both kinds can only come from a state saved
+        # while the scheduled value was exactly 0 (equal rows are shared): set_weight_decay refuses it.
+        if self._decay_names is None:
+            self._decay_names = {nm for nm, key in per_name.items() if key[1] != 0.0}
+        mask = torch.zeros(MAX_PARAM_GROUPS, dtype=torch.float32)
+        kinds = {}
+        for nm, r in self._group_row_of.items():
+            kinds.setdefault(r, set()).add(nm in self._decay_names)
+        for r, k in kinds.items():
+            mask[r] = 1.0 if k == {True} else 0.0
+        self._mixed_rows = any(len(k) == 2 for k in kinds.values())
+        if self._decay_rows is None:
+            self._decay_rows = mask.to(self._group_table_full.device)
+        else:
+            self._decay_rows.copy_(mask)
 
     def set_lr(self, lr):
         self.lr.fill_(float(lr))
+
+    def set_weight_decay(self, wd):
+        """Write ``wd`` into the weight-decay column of every row of the device table whose parameters were decayed at
+        construction (no-decay rows stay 0; with ``param_groups`` of several decays all of them take ``wd``, as the
+        reference's scheduler overwrites its group).  Device memory, like ``set_lr``: a captured optimizer graph replays
+        with the new value.  ``state_dict()`` carries it (``param_groups`` is read from the table)."""
+        if not self._grouped:
+            raise RuntimeError("FlatAdamW.set_weight_decay: this optimizer runs fv_adamw_flat, whose weight decay is a kernel "
+                               "argument that a captured graph replays as captured -- build it with "
+                               "scheduled_weight_decay=True (or param_groups / max_grad_norm / skip_nonfinite), which "
+                               "select the grouped kernel and its device table")
+        if self._mixed_rows:
+            raise RuntimeError("FlatAdamW.set_weight_decay: the loaded state shares a table row between decayed and no-decay "
+                               "parameters (it was saved at a scheduled weight decay of exactly 0)")
+        with torch.no_grad():
+            self._group_table_full[:, 1].copy_(self._decay_rows * float(wd))
 
     def set_max_grad_norm(self, v):
         if self.max_norm is None:

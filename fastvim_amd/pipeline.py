@@ -31,9 +31,11 @@ from .graph_chain import ChainStep, restore_training_state, snapshot_training_st
 
 
 class SegmentedTrainStep(ChainStep):
-    """``model`` must expose ``_embed / _run_layers / _final / _head``: fastvim_amd.fastvim.VisionMamba, the channel models,
-    and the un-pooled baseline fastvim_amd.vim.VisionMamba (whose ``fused_cls`` puts its class token's bookkeeping on the HIP
-    path; ``mixup`` / ``erase`` / uint8 batches as for FastVim, no ``hcs``).
+    """``model`` must expose ``_embed / _run_layers / _final / _head``: fastvim_amd.fastvim.VisionMamba, the channel models
+    (FastChannelVim and its 2-D compress variant), and the two un-pooled baselines with a middle class token, whose
+    ``fused_cls`` puts that token's bookkeeping on the HIP path: fastvim_amd.vim.VisionMamba (``mixup`` / ``erase`` / uint8
+    batches as for FastVim, no ``hcs``) and fastvim_amd.models_channel_mamba.VisionMamba (ChannelVim: ``hcs`` and uint8
+    batches as for FastChannelVim; the class position follows the channel count of the family).
     ``loss_fn(logits, target) -> scalar``.  ``x`` / ``target`` are the static input buffers the graphs read; copy
     new batches into them between steps.  ``x`` holds normalised float pixels, or -- after
     ``fastvim_amd.pixels.attach_pixel_norm(model, mean, std)`` -- the uint8 batch itself, normalised inside the patch unfold.
@@ -95,8 +97,9 @@ class SegmentedTrainStep(ChainStep):
         self.hcs = hcs
         if hcs is not None and "hcs" not in inspect.signature(model._embed).parameters:
             raise TypeError("SegmentedTrainStep: hcs= needs a model whose _embed takes the sampler (`_embed(x, hcs=None)`: "
-                            "fastvim_amd.models_channel_mamba_faster.VisionMamba; fastvim.VisionMamba and vim.VisionMamba "
-                            "embed all channels)")
+                            "the channel models fastvim_amd.models_channel_mamba_faster.VisionMamba, its 2-D compress variant and "
+                            "fastvim_amd.models_channel_mamba.VisionMamba; fastvim.VisionMamba and vim.VisionMamba embed all "
+                            "channels)")
         if hcs is not None:
             hcs.block(x.device)                          # the index array exists before any capture
         super().__init__(flat, opt, x, n_segments, use_graph)

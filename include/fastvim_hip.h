@@ -109,7 +109,10 @@ const char* fv_last_error(void);
  *      Later, still 3: fv_vim_cls_tokens_fwd, fv_vim_cls_tokens_bwd, fv_add_norm_row_fwd and fv_add_norm_row_bwd were ADDED
  *      (the supervised Vim baseline: its class token put among the patch tokens with the position table, and its final
  *      add + norm of the class row alone); no existing entry point changed -- fv_add_norm_fwd / _bwd run the kernels they
- *      ran, whose bodies the row forms share. */
+ *      ran, whose bodies the row forms share.
+ *      Later, still 3: fv_chan_cls_tokens_fwd and fv_chan_cls_tokens_bwd were ADDED (the ChannelVim baseline: its class
+ *      token put among channel tokens that already carry their position rows -- rows moved, nothing added); no existing
+ *      entry point changed: fv_vim_cls_tokens_* keep adding their table and writing fp32. */
 #define FV_ABI_VERSION 3
 int fv_version(void);
 
@@ -1210,6 +1213,28 @@ int fv_add_norm_row_bwd(const void* dy, int dy_dtype, const void* r, int r_dtype
                         const float* rstd, const float* row_scale, void* dhidden, int dhidden_dtype, void* dresidual,
                         int dresidual_dtype, float* partial_dw, float* partial_db, int batch, int rows, int position, int N,
                         int is_rms_norm, fv_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * The class token of the ChannelVim baseline (csrc/chan_tokens.hip): B = batch samples, M = len channel tokens (P patches
+ * times the channels of this forward pass; pos_embed is already in them), p = position of the class token among the
+ * M + 1 rows (0 <= p <= M).  dtype FV_F32 or FV_BF16, of the tokens on BOTH sides; dim % 4 == 0; B (M + 1) < 2^31.
+ *
+ * fv_chan_cls_tokens_fwd: out (B, M + 1, dim) dtype from y (B, M, dim) dtype:
+ *   out[b, j] = (j == p ? cls_token rounded to dtype : y[b, j - (j > p)]) -- the values of
+ *   `cat((x[:, :p], cls_token.expand(B, -1, -1).to(x.dtype), x[:, p:]), 1)`.  The token rows are MOVED as bits: no
+ *   arithmetic touches them (-0.0 stays -0.0).  cls_token (dim) fp32.  A thread moves 16 bytes (8 for bf16 when
+ *   dim % 8 != 0).
+ * fv_chan_cls_tokens_bwd: ONE launch.  dout (B, M + 1, dim) dtype; dy (B, M, dim) dtype: dy[b, i] = the bits of
+ *   dout[b, i + (i >= p)], one thread per 16 bytes of dy (a full-grid copy); dcls_token (dim) fp32 = sum over
+ *   b = 0 .. B-1 of dout[b, p, :], added in fp64 in that order, rounded once -- by dim / 4 (bf16, dim % 8 == 0: dim / 8)
+ *   threads in the first workgroups of the same grid.
+ * No atomics, no partial buffer, no host synchronisation: safe under stream capture; the same inputs give the same bits.
+ * Alignment: every buffer 4 bytes.
+ * ---------------------------------------------------------------------- */
+int fv_chan_cls_tokens_fwd(const void* y, int dtype, const float* cls_token, void* out, int batch, int len, int dim,
+                           int position, fv_stream_t stream);
+int fv_chan_cls_tokens_bwd(const void* dout, void* dy, int dtype, float* dcls_token, int batch, int len, int dim,
+                           int position, fv_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Device-side geometry of the uint8 loaders: bicubic resize, crop window and horizontal flip of decoded 8-bit images,
